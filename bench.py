@@ -1,13 +1,19 @@
 #!/usr/bin/env python
 """images/sec of the full student+teacher ALDI step (R50-FPN, 1333x800, ALDI++ config) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one ALDI iteration on one synthetic batch per GPU (2 labeled_strong + 2 unlabeled
 weak/strong pairs, inputs resident in HBM): EMA tick, source micro-step fwd+bwd, teacher
 inference + pseudo-labels, student distill micro-step fwd+bwd with the four soft losses, one
 gradient all-reduce (N>1), SGD.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of
+its own: the in-situ per-kernel roofline (three extra eager steps) and the CPU oracle baseline.
+--dump-outputs DIR writes what the last timed step computed (losses, pseudo labels, a fixed sample of
+the student's and the teacher's updated state) as DIR/<name>.npy, for output-for-output comparisons
+of two builds: the inputs and the initial weights are seeded, identical from run to run.
 """
 import argparse
 import copy
@@ -514,6 +520,41 @@ def _traffic_per_launch(tj, family, launches):
     return round(f["hbm_bytes_per_launch"])
 
 
+DUMP_STATE_SAMPLE = 2 << 20        # elements of each model's flat state dumped (a fixed seeded sample): 2 x 8 MB of float32 + the positions
+
+
+def dump_outputs(tr, out_dir):
+    """What the last timed step handed its caller, as out_dir/<name>.npy: the loss dict (float64, one file per loss), the teacher's
+    pseudo labels of that step (device buffers of fixed shape; integer fields as float64) and the student's and the teacher's flat fp32
+    state after the step's SGD / EMA update -- the same DUMP_STATE_SAMPLE positions of each (seeded, so every run and every build of
+    one workload picks the same ones; all of it when the state is smaller)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {}
+    for k, v in tr._trainer.last_loss_dict.items():
+        arrays[k if k.startswith("loss") else "loss_" + k] = np.array([float(v)], dtype=np.float64)
+    pseudo = tr.ema.model._last_inference.pseudo
+    for k in sorted(pseudo):
+        t = pseudo[k].detach().cpu()
+        arrays["pseudo_" + k] = t.numpy().astype(np.float32 if t.is_floating_point() else np.float64)
+    picks = {}
+    for tag, model in (("student", tr.model), ("teacher", tr.ema.model)):
+        state = model.weights.master.detach()
+        n = state.numel()
+        if n > DUMP_STATE_SAMPLE:
+            if n not in picks:
+                picks[n] = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_STATE_SAMPLE].sort().values
+                arrays[tag + "_state_index"] = picks[n].numpy().astype(np.float64)
+            state = state[picks[n].to(state.device)]
+        arrays[tag + "_state"] = state.float().cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    print(f"bench.py: {len(arrays)} arrays, {total / 2**20:.1f} MB -> {out_dir}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -532,6 +573,9 @@ def main():
                     "(BASELINE configs[1]); 6 = the reference's shipped per-GPU batch (IMS_PER_BATCH 48 on 8 GPUs), a secondary figure")
     ap.add_argument("--workload", default="r50_fpn", choices=["r50_fpn", "vitdet_b", "convnext_l", "detr"],
                     help="r50_fpn = the headline configuration (default); vitdet_b = BASELINE cfg 4 (SURVEY 8(f) rank 1), reported beside it")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the in-situ roofline profile "
+                    "(unless --no-profile) and the CPU oracle baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     vitdet = args.workload == "vitdet_b"
     if args.workload != "r50_fpn":
@@ -635,6 +679,8 @@ def main():
     err = int(getattr(tr.model.engine, "err", 0)) | int(getattr(tr.ema.model.engine, "err", 0))
     losses = {k: float(v) for k, v in tr._trainer.last_loss_dict.items()}
     pl_count = tr.ema.model._last_inference.pseudo["count"].tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)
 
     fs_stats = dict(getattr(getattr(tr._trainer, "_fused_step", None), "stats", {}))
     if args.workload == "detr" and not args.sequential and getattr(tr._trainer, "_detr_fused_steps", 0) > 0:
@@ -663,7 +709,7 @@ def main():
                       "pseudo_labels_per_image": pl_count, "schedule": schedule, "weights": f"random-init {arch_name} (synthetic)", "error_flag": err, "init_steps": init_steps,
                       "step_graphs": dict(getattr(getattr(tr._trainer, "_fused_step", None), "stats", {}))},
            "final_losses": {k: round(v, 5) for k, v in losses.items()}}
-    if rank == 0 and world == 1 and not args.no_profile:
+    if args.full and rank == 0 and world == 1 and not args.no_profile:
         fs = getattr(tr._trainer, "_fused_step", None)
         graph_was = fs.graph_enabled if fs is not None else False
         if fs is not None:
@@ -756,7 +802,7 @@ def main():
         if not headline:
             out["roofline"]["dense_ms_per_step"] = round(ig["ms"] + wg["ms"], 3)
             out["roofline"]["note"] = "the families timed are the dense kernels this workload shares with the headline step (ops.conv2d / conv_wgrad); its attention / normalisation kernels are in the kernel-trace summary under profiles/"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, args.height, args.width)
     if rank == 0:
         print(json.dumps(out))

@@ -657,10 +657,37 @@ def g11(m):
     save("g11_discriminators_deep", **out)
 
 
+# ----------------------------------------------------------------------------
+# G13  the reference's configs/cityscapes/ALDI-Best-Cityscapes.yaml (with its _BASE_ chain) loaded through aldi_amd.config:
+#      every key that configures the step (MODEL / SOLVER / DOMAIN_ADAPT / EMA / VIT), flattened
+# ----------------------------------------------------------------------------
+def g13(m):
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from aldi_amd.config import add_aldi_config, get_cfg
+    cfg = get_cfg()
+    add_aldi_config(cfg)
+    cfg.merge_from_file(os.path.join(REF, "configs", "cityscapes", "ALDI-Best-Cityscapes.yaml"))
+
+    def flat(node, pre=""):
+        out = {}
+        for k, v in node.items():
+            if hasattr(v, "items"):
+                out.update(flat(v, pre + k + "."))
+            else:
+                out[pre + k] = v
+        return out
+    res = {k: v for k, v in flat(cfg).items()
+           if k.split(".")[0] in ("MODEL", "SOLVER", "DOMAIN_ADAPT", "EMA", "VIT") and not k.startswith("MODEL.ROI_MASK_HEAD")}
+    with open(os.path.join(HERE, "g13_reference_best_cityscapes_cfg.json"), "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+    print("wrote g13_reference_best_cityscapes_cfg.json")
+
+
 if __name__ == "__main__":
     random.seed(0)
     mods = import_reference()
     only = sys.argv[1:]
-    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11):
+    for fn in (g1, g2, g3, g4, g5, g6, g7, g8, g9, g10, g11, g13):
         if not only or fn.__name__ in only:
             fn(mods)

@@ -43,9 +43,10 @@ def test_yaml_base_inheritance_and_overrides():
         cfg.SOLVER.BASE_LR = 1.0
 
 
-def test_fast_path_is_the_default_and_the_reference_yaml_selects_it():
-    """SOLVER.FUSED_STEP / STEP_GRAPH are on unless switched off; (in the build container, where /root/reference exists) the reference's own
-    ALDI-Best-Cityscapes.yaml loads unmodified, and into the same model / solver / adaptation / EMA configuration as the repository's copy"""
+def test_fast_path_is_the_default_and_the_reference_yaml_selects_it(golden_dir):
+    """SOLVER.FUSED_STEP / STEP_GRAPH are on unless switched off; the reference's own ALDI-Best-Cityscapes.yaml loads unmodified, and
+    into the same model / solver / adaptation / EMA configuration as the repository's copy (g13: the reference YAML's step keys as
+    aldi_amd.config loaded them, recorded by tests/golden/make_golden.py)"""
     from aldi_amd.config import add_aldi_config, get_cfg
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -65,10 +66,9 @@ def test_fast_path_is_the_default_and_the_reference_yaml_selects_it():
         return out
     mine = load(os.path.join(root, "configs", "cityscapes", "ALDI-Best-Cityscapes.yaml"))
     assert mine.SOLVER.FUSED_STEP is True and mine.SOLVER.STEP_GRAPH is True
-    ref_path = "/root/reference/configs/cityscapes/ALDI-Best-Cityscapes.yaml"
-    if not os.path.exists(ref_path):
-        return
-    a, b = flat(mine), flat(load(ref_path))
+    with open(os.path.join(golden_dir, "g13_reference_best_cityscapes_cfg.json")) as f:
+        b = json.load(f)
+    a = {k: json.loads(json.dumps(v)) for k, v in flat(mine).items()}         # tuples -> lists, as the fixture holds them
     # everything that configures the STEP is identical; what differs names data that does not exist here (dataset names, input sizes of
     # the host-side resize, augmentation switches, evaluation / checkpoint periods, output directory, the initial checkpoint file)
     step_keys = [k for k in b if k.split(".")[0] in ("MODEL", "SOLVER", "DOMAIN_ADAPT", "EMA", "VIT") and not k.startswith("MODEL.ROI_MASK_HEAD")]
