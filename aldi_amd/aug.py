@@ -14,6 +14,7 @@ Same class names / constructor arguments as the reference; `apply_image` takes a
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import random
 from typing import List, Optional, Sequence, Tuple
@@ -102,16 +103,16 @@ class RandomEraseTransform:
     def __init__(self, sl=0.02, sh=0.4, r1=0.3, r2=3.3, value="random"):
         self.sl, self.sh, self.r1, self.r2, self.value = sl, sh, r1, r2, value
 
-    def draw(self, imgh: int, imgw: int) -> Optional[Tuple[int, int, int, int]]:
+    def draw(self, imgh: int, imgw: int, py_rng=random) -> Optional[Tuple[int, int, int, int]]:
         for _ in range(100):
             area = imgw * imgh
-            target_area = random.uniform(self.sl, self.sh) * area
-            aspect_ratio = random.uniform(self.r1, self.r2)
+            target_area = py_rng.uniform(self.sl, self.sh) * area
+            aspect_ratio = py_rng.uniform(self.r1, self.r2)
             h = int(round(math.sqrt(target_area * aspect_ratio)))
             w = int(round(math.sqrt(target_area / aspect_ratio)))
             if w > 1 and h > 1 and w < imgw and h < imgh:
-                h0 = random.randint(0, imgh - h - 1)
-                w0 = random.randint(0, imgw - w - 1)
+                h0 = py_rng.randint(0, imgh - h - 1)
+                w0 = py_rng.randint(0, imgw - w - 1)
                 return h0, w0, h, w
         return None
 
@@ -189,7 +190,12 @@ def get_strong_augs(cfg, labeled: bool) -> List[RandomApply]:
 
 
 def strong_view(img_weak_hwc: torch.Tensor, augs: Sequence[RandomApply], chw: bool = True) -> torch.Tensor:
-    """weak view (HWC uint8, device) -> strong view; `chw` returns the (3, H, W) layout dataset dicts carry"""
+    """weak view (HWC uint8, device) -> strong view; `chw` returns the (3, H, W) layout dataset dicts carry.  A chain the
+    batched kernels run (`recognise_chain`) goes through `strong_views`; anything else through the per-op kernels above.
+    Both consume the generators identically and give the same bytes."""
+    _check(img_weak_hwc)
+    if recognise_chain(augs) is not None:
+        return strong_views([img_weak_hwc], augs, chw=False, out_chw=chw)[0]
     img = img_weak_hwc
     for a in augs:
         img = a.apply_image(img)
@@ -199,3 +205,267 @@ def strong_view(img_weak_hwc: torch.Tensor, augs: Sequence[RandomApply], chw: bo
     out = torch.empty((3, H, W), dtype=torch.uint8, device=img.device)
     L.call("aldi_aug_hwc_to_chw", _p(img), _p(out), H, W, ops.stream_ptr())
     return out
+
+
+
+# ------------------------------------------------------------------------------------------------ batched strong views
+# N weak views of any sizes -> N strong views in at most three launches (csrc/aug.hip: batch_sums_kernel, fill_kernel,
+# view_kernel).  The host only draws: the gates, weights, sigma, rects and MIC mask as `apply_image` would, and for every erase
+# fill a snapshot of numpy's MT19937 state every FILL_SEG_WORDS outputs while the state is skipped past the fill
+# (aldi_np_mt_advance).  The device replays the fill from those snapshots: the ~0.5 M doubles per 1333x800 view are never
+# drawn or copied by the host.
+FILL_SEG_WORDS = 624 * 16                     # 32-bit outputs per fill job (16 state refills; even: a job never splits a double)
+_HALO = 8                                     # ALDI_AUG_HALO: the largest blur radius of the fused kernel
+_COLOUR, _GRAY, _BLUR, _CHW_IN, _CHW_OUT = 1, 2, 4, 8, 16
+_TH, _TW, _SUM_CHUNK = 16, 64, 32768
+
+
+class _AugDesc(ctypes.Structure):
+    """aldi_aug_desc (include/aldi_hip.h)"""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("sum", ctypes.c_ulonglong),
+                ("wc", ctypes.c_double), ("wb", ctypes.c_double), ("ws", ctypes.c_double), ("wg", ctypes.c_double),
+                ("taps", ctypes.c_double * (_HALO + 1)), ("fill_off", ctypes.c_long * 3),
+                ("H", ctypes.c_int), ("W", ctypes.c_int), ("flags", ctypes.c_int), ("radius", ctypes.c_int),
+                ("rect", (ctypes.c_int * 4) * 3), ("nerase", ctypes.c_int), ("mh", ctypes.c_int), ("mw", ctypes.c_int),
+                ("tile_begin", ctypes.c_int), ("sum_begin", ctypes.c_int), ("sum_blocks", ctypes.c_int)]
+
+
+class _FillJob(ctypes.Structure):
+    """aldi_aug_fill_job (include/aldi_hip.h)"""
+    _fields_ = [("snap", ctypes.c_void_p), ("out_off", ctypes.c_long), ("pos", ctypes.c_int), ("ndoubles", ctypes.c_int)]
+
+
+class StrongParams:
+    """What one image's pass through the chain drew.  colour = (contrast, brightness, saturation) weights or None, gray =
+    the grayscale stage's saturation weight or None, sigma = blur sigma or None, erases = [((h0, w0, h, w), snaps [k][624]
+    uint32, snap_pos [k] int32)] (snapshot j = numpy's state before output j * FILL_SEG_WORDS of the fill), mic = the bool
+    block mask (True = keep) or None."""
+    __slots__ = ("H", "W", "colour", "gray", "sigma", "erases", "mic")
+
+    def __init__(self, H: int, W: int, colour=None, gray=None, sigma=None, erases=(), mic=None):
+        self.H, self.W, self.colour, self.gray, self.sigma, self.erases, self.mic = H, W, colour, gray, sigma, list(erases), mic
+
+    def ops(self) -> List[tuple]:
+        """the oracle's op list (oracle/aug_ops.py draw_strong_params) without the fill arrays: ("erase", rect)"""
+        out: List[tuple] = []
+        if self.colour is not None:
+            out += [("contrast", self.colour[0]), ("brightness", self.colour[1]), ("saturation", self.colour[2])]
+        if self.gray is not None:
+            out.append(("saturation", self.gray))
+        if self.sigma is not None:
+            out.append(("blur", self.sigma))
+        out += [("erase", rect) for rect, _, _ in self.erases]
+        if self.mic is not None:
+            out.append(("mic", self.mic))
+        return out
+
+
+def _radius(sigma: float) -> int:
+    return int(4.0 * float(sigma) + 0.5)
+
+
+def recognise_chain(augs) -> Optional[List[tuple]]:
+    """[(stage, prob, transforms)] when `augs` is a chain the batched kernels run -- build_strong_augmentation's stages in its
+    order, each optional: the colour triple, a lone RandomSaturation (grayscale), a blur whose radius stays within the halo,
+    up to three random-value erases, one MIC -- else None (the per-op path takes it)."""
+    rank = {"colour": 0, "gray": 1, "blur": 2, "erase": 3, "mic": 4}
+    plan, last = [], -1
+    for ra in augs:
+        if type(ra) is not RandomApply:
+            return None
+        subs = list(ra.aug) if isinstance(ra.aug, (list, tuple)) else [ra.aug]
+        types = tuple(type(a) for a in subs)
+        if types == (RandomContrast, RandomBrightness, RandomSaturation):
+            kind = "colour"
+        elif types == (RandomSaturation,):
+            kind = "gray"
+        elif types == (RandomBlurTransform,) and 0 < subs[0].sigma[0] <= subs[0].sigma[1] and _radius(subs[0].sigma[1]) <= _HALO:
+            kind = "blur"
+        elif types == (RandomEraseTransform,) and subs[0].value == "random":
+            kind = "erase"
+        elif types == (MICTransform,):
+            kind = "mic"
+        else:
+            return None
+        if rank[kind] < last or (rank[kind] == last and kind != "erase"):
+            return None
+        last = rank[kind]
+        plan.append((kind, ra.prob, subs))
+    if sum(1 for k, _, _ in plan if k == "erase") > 3:
+        return None
+    return plan
+
+
+def np_mt_advance(np_rng, n_words: int, seg: int = FILL_SEG_WORDS):
+    """Advance numpy's legacy MT19937 (`np.random` or a RandomState) by n_words 32-bit outputs -- what rand(n_words // 2)
+    consumes -- without drawing; -> (snaps [k][624] uint32, snap_pos [k] int32), the state before outputs 0, seg, 2 seg, ..."""
+    if isinstance(np_rng, np.random.Generator):
+        raise TypeError("the strong augmentation replays numpy's legacy MT19937 stream: pass np.random or a RandomState, "
+                        "not a numpy Generator")
+    st = np_rng.get_state()
+    if st[0] != "MT19937":
+        raise TypeError(f"unsupported numpy bit generator {st[0]}")
+    key = np.array(st[1], dtype=np.uint32)
+    pos = ctypes.c_int(int(st[2]))
+    nsnap = (n_words + seg - 1) // seg if seg > 0 else 0
+    snaps = np.empty((nsnap, 624), dtype=np.uint32)
+    snap_pos = np.empty(nsnap, dtype=np.int32)
+    L.check(L.lib.aldi_np_mt_advance(key.ctypes.data, ctypes.byref(pos), int(n_words), int(seg), snaps.ctypes.data,
+                                     snap_pos.ctypes.data, nsnap), "aldi_np_mt_advance")
+    np_rng.set_state((st[0], key, pos.value, st[3], st[4]))
+    return snaps, snap_pos
+
+
+def draw_strong_params(augs, H: int, W: int, np_rng=np.random, py_rng=random) -> StrongParams:
+    """Walk the chain for one H x W image, consuming `np_rng` (np.random or a RandomState) and `py_rng` (random or a
+    random.Random) in exactly the order and amounts sequential `apply_image` calls do: every gate, the colour weights (the
+    grayscale stage's uniform(0, 0) included), sigma, the erase rejection loop (a failed one consumes no fill), each fill
+    skipped past with snapshots instead of `rand`, the MIC mask's `rand`."""
+    plan = recognise_chain(augs)
+    if plan is None:
+        raise ValueError("draw_strong_params: not a chain of build_strong_augmentation / get_strong_augs stages")
+    if isinstance(np_rng, np.random.Generator):
+        raise TypeError("draw_strong_params: pass np.random or a RandomState, not a numpy Generator")
+    p = StrongParams(H, W)
+    for kind, prob, subs in plan:
+        if not np_rng.uniform(0, 1.0) < prob:
+            continue
+        if kind == "colour":
+            p.colour = tuple(float(np_rng.uniform(a.intensity_min, a.intensity_max)) for a in subs)
+        elif kind == "gray":
+            p.gray = float(np_rng.uniform(subs[0].intensity_min, subs[0].intensity_max))
+        elif kind == "blur":
+            p.sigma = py_rng.uniform(subs[0].sigma[0], subs[0].sigma[1])
+        elif kind == "erase":
+            rect = subs[0].draw(H, W, py_rng)
+            if rect is not None:
+                snaps, snap_pos = np_mt_advance(np_rng, 2 * rect[2] * rect[3] * 3)
+                p.erases.append((rect, snaps, snap_pos))
+        else:
+            m = subs[0]
+            p.mic = np_rng.rand(round(H / m.block_size), round(W / m.block_size)) > m.ratio
+    return p
+
+
+def _upload(dst: torch.Tensor, src: torch.Tensor):
+    """the batch's one host -> device copy (descriptors, fill jobs, MT snapshots, MIC masks) from pinned memory"""
+    dst.copy_(src, non_blocking=True)
+
+
+def _align(n: int, a: int = 256) -> int:
+    return (n + a - 1) // a * a
+
+
+def launch_strong_views(weak_views: Sequence[torch.Tensor], params: Sequence[StrongParams], chw: bool = True,
+                        out_chw: Optional[bool] = None) -> List[torch.Tensor]:
+    """the device half of `strong_views`: one pinned upload, then at most three launches on the current stream"""
+    out_chw = chw if out_chw is None else out_chw
+    n = len(weak_views)
+    if n == 0:
+        return []
+    if len(params) != n:
+        raise ValueError("launch_strong_views: one StrongParams per view")
+    sizes = []
+    for v, p in zip(weak_views, params):
+        if not (v.is_cuda and v.dtype == torch.uint8 and v.dim() == 3 and v.is_contiguous() and v.shape[0 if chw else 2] == 3):
+            raise ValueError(f"strong_views expects contiguous CUDA uint8 {'CHW' if chw else 'HWC'} images with 3 channels")
+        H, W = (int(v.shape[1]), int(v.shape[2])) if chw else (int(v.shape[0]), int(v.shape[1]))
+        if (H, W) != (p.H, p.W):
+            raise ValueError(f"strong_views: parameters drawn for {p.H}x{p.W}, image is {H}x{W}")
+        sizes.append((H, W))
+    # layout of the upload: [descriptors][fill jobs][snapshots][MIC masks]
+    njobs = sum(len(sn) for p in params for _, sn, _ in p.erases)
+    off_jobs = _align(n * ctypes.sizeof(_AugDesc))
+    off_snaps = _align(off_jobs + njobs * ctypes.sizeof(_FillJob))
+    off_masks = _align(off_snaps + njobs * 624 * 4)
+    mask_bytes = [0 if p.mic is None else int(np.asarray(p.mic).size) for p in params]
+    total = off_masks + sum(mask_bytes)
+    host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    dev = torch.empty(total, dtype=torch.uint8, device=weak_views[0].device)
+    hbuf, dbase = host.numpy(), dev.data_ptr()
+    descs = (_AugDesc * n).from_buffer(hbuf)
+    ctypes.memset(ctypes.addressof(descs), 0, off_jobs)
+    jobs = (_FillJob * njobs).from_buffer(hbuf, off_jobs) if njobs else None
+    snaps = hbuf[off_snaps: off_snaps + njobs * 624 * 4].view(np.uint32).reshape(njobs, 624)
+    outs = [torch.empty((3, H, W) if out_chw else (H, W, 3), dtype=torch.uint8, device=v.device) for v, (H, W) in zip(weak_views, sizes)]
+    tiles = sum_blocks = arena_bytes = j = 0
+    moff = off_masks
+    for i, (v, p, (H, W)) in enumerate(zip(weak_views, params, sizes)):
+        d = descs[i]
+        d.src, d.dst, d.H, d.W = v.data_ptr(), outs[i].data_ptr(), H, W
+        d.flags = (_CHW_IN if chw else 0) | (_CHW_OUT if out_chw else 0)
+        if p.colour is not None:
+            d.flags |= _COLOUR
+            d.wc, d.wb, d.ws = (float(w) for w in p.colour)
+            d.sum_begin, d.sum_blocks = sum_blocks, (3 * H * W + _SUM_CHUNK - 1) // _SUM_CHUNK
+            sum_blocks += d.sum_blocks
+        else:
+            d.sum_begin = sum_blocks
+        if p.gray is not None:
+            d.flags |= _GRAY
+            d.wg = float(p.gray)
+        if p.sigma is not None:
+            w = gaussian_weights(p.sigma)
+            r = (len(w) - 1) // 2
+            if r > _HALO:
+                raise ValueError(f"strong_views: blur radius {r} (sigma {p.sigma}) exceeds the fused kernel's halo {_HALO}")
+            d.flags |= _BLUR
+            d.radius = r
+            for k in range(r + 1):
+                d.taps[k] = float(w[k])
+        if len(p.erases) > 3:
+            raise ValueError("strong_views: at most three erase rects per image")
+        d.nerase = len(p.erases)
+        for e, (rect, sn, sp) in enumerate(p.erases):
+            h0, w0, h, w = (int(x) for x in rect)
+            if not (h0 >= 0 and w0 >= 0 and h > 0 and w > 0 and h0 + h <= H and w0 + w <= W):
+                raise ValueError(f"strong_views: erase rect {rect} outside the {H}x{W} image")
+            nd = h * w * 3
+            if len(sn) != (2 * nd + FILL_SEG_WORDS - 1) // FILL_SEG_WORDS:
+                raise ValueError("strong_views: fill snapshots do not cover the erase rect")
+            d.rect[e][0], d.rect[e][1], d.rect[e][2], d.rect[e][3] = h0, w0, h, w
+            d.fill_off[e] = arena_bytes
+            for k in range(len(sn)):
+                jb = jobs[j]
+                jb.snap = dbase + off_snaps + j * 624 * 4
+                jb.out_off = arena_bytes + k * (FILL_SEG_WORDS // 2)
+                jb.pos = int(sp[k])
+                jb.ndoubles = min(FILL_SEG_WORDS // 2, nd - k * (FILL_SEG_WORDS // 2))
+                j += 1
+            snaps[j - len(sn): j] = sn
+            arena_bytes += nd
+        if p.mic is not None:
+            m = np.ascontiguousarray(p.mic, dtype=np.uint8)
+            if m.ndim != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+                raise ValueError(f"strong_views: MIC mask of shape {m.shape} for a {H}x{W} image (cv2.resize needs a non-empty mask)")
+            d.mh, d.mw = m.shape
+            hbuf[moff: moff + m.size] = m.reshape(-1)
+            d.mask = dbase + moff
+            moff += m.size
+        d.tile_begin = tiles
+        tiles += ((H + _TH - 1) // _TH) * ((W + _TW - 1) // _TW)
+    del descs, jobs                                       # (ctypes views of the pinned buffer)
+    arena = torch.empty(max(arena_bytes, 1), dtype=torch.uint8, device=dev.device)
+    _upload(dev, host)
+    st = ops.stream_ptr()
+    if sum_blocks:
+        L.call("aldi_aug_batch_sums", dbase, n, sum_blocks, st)
+    if njobs:
+        L.call("aldi_aug_batch_fills", dbase + off_jobs, njobs, arena.data_ptr(), st)
+    L.call("aldi_aug_batch_view", dbase, n, tiles, arena.data_ptr(), st)
+    return outs
+
+
+def strong_views(weak_views: Sequence[torch.Tensor], augs, chw: bool = True, np_rng=np.random, py_rng=random, stream=None,
+                 out_chw: Optional[bool] = None, params: Optional[Sequence[StrongParams]] = None) -> List[torch.Tensor]:
+    """Batched strong views: `weak_views` are device uint8 images, (3, H, W) when `chw` else (H, W, 3), sizes may differ.
+    Draws each image's parameters in order (`draw_strong_params`; or takes `params`), then runs the batch in at most three
+    launches on `stream` (default: the current stream).  Outputs are in the input layout unless `out_chw` says otherwise and
+    equal, byte for byte, sequential per-op `strong_view` calls consuming the same generators."""
+    if params is None:
+        params = [draw_strong_params(augs, *((int(v.shape[1]), int(v.shape[2])) if chw else (int(v.shape[0]), int(v.shape[1]))),
+                                     np_rng=np_rng, py_rng=py_rng) for v in weak_views]
+    if stream is None:
+        return launch_strong_views(weak_views, params, chw, out_chw)
+    with torch.cuda.stream(stream):
+        return launch_strong_views(weak_views, params, chw, out_chw)

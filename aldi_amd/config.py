@@ -176,6 +176,9 @@ def add_aldi_config(cfg: CfgNode):
     _C.AUG.UNLABELED_MIC_AUG = False
     _C.AUG.MIC_RATIO = 0.5
     _C.AUG.MIC_BLOCK_SIZE = 32
+    # the strong views of the training loader from the reference's chain (get_strong_augs of the keys above), built on the
+    # device in three launches per batch (aldi_amd/dataloader.py DeviceStrongAugLoader); off: the loader's own views
+    _C.AUG.DEVICE_STRONG = False
 
     _C.EMA = CN()
     _C.EMA.ENABLED = False

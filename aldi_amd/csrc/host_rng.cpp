@@ -433,3 +433,28 @@ extern "C" int aldi_torch_rng_prefetch_hits(void) {
     std::lock_guard<std::mutex> lock(g_set.mu);
     return (int)(g_stream_hits & 0x7fffffff);
 }
+
+// numpy's legacy RandomState (MT19937: key[624] + pos) advanced by n 32-bit outputs, as n / 2 calls of random_sample would
+// leave it, without tempering or converting anything.  Every `seg` outputs (offsets 0, seg, 2 seg, ... < n) the state as it is
+// at that point is written to snaps[k][624] / snap_pos[k]: the device replays segment k of the stream from it
+// (aug.hip fill_kernel), so a long erase fill runs on many workgroups while the host only skips through the refills.
+// numpy's pos maps to the engine above as next = pos, left = 625 - pos (pos = 624: the next draw refills first).
+extern "C" int aldi_np_mt_advance(unsigned int* key, int* pos, long n, long seg, unsigned int* snaps, int* snap_pos, long max_snaps) {
+    if (!key || !pos || *pos < 0 || *pos > MT_N || n < 0 || (seg > 0 && n > 0 && (!snaps || !snap_pos)))
+        return aldi_set_error_msg(ALDI_ERR_ARG, "np_mt_advance: bad args");
+    const long nsnap = seg > 0 ? (n + seg - 1) / seg : 0;
+    if (nsnap > max_snaps) return aldi_set_error_msg(ALDI_ERR_ARG, "np_mt_advance: snapshot buffer too small");
+    Mt mt;
+    memcpy(mt.s, key, sizeof(mt.s));
+    mt.next = (uint64_t)*pos;
+    mt.left = MT_N + 1 - *pos;
+    for (long k = 0; k < nsnap; ++k) {
+        memcpy(snaps + (size_t)k * MT_N, mt.s, sizeof(mt.s));
+        snap_pos[k] = (int)mt.next;
+        mt.discard(k + 1 < nsnap ? seg : n - k * seg);
+    }
+    if (nsnap == 0) mt.discard(n);
+    memcpy(key, mt.s, sizeof(mt.s));
+    *pos = (int)mt.next;
+    return ALDI_OK;
+}

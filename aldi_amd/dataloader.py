@@ -4,7 +4,10 @@
 (labeled_weak, labeled_strong, unlabeled_weak, unlabeled_strong); weak = deepcopy with
 "image" <- "img_weak"; unlabeled_weak is produced whenever ANY unlabeled content is requested."""
 import copy
+import random
+from concurrent.futures import ThreadPoolExecutor
 
+import numpy as np
 import torch
 
 from . import synthetic
@@ -69,3 +72,99 @@ class SyntheticDetectionLoader:
                 batch.append({"image": synthetic.strong_view(img, g), WEAK_IMG_KEY: img, "instances": inst})
             it += 1
             yield batch
+
+
+def device_strong_seed(base: int, rank: int, labeled: bool) -> int:
+    """the private draw seed of one rank's labeled / unlabeled DeviceStrongAugLoader (`base` = cfg.SEED, or 0 when unset)"""
+    return (base * 1000003 + (3000 if labeled else 4000) + 17 * rank) % 2 ** 32
+
+
+class DeviceStrongAugLoader:
+    """Wraps a loader that yields lists of dicts carrying `img_weak` (uint8 CHW, host or device) and builds every strong view on
+    the device (aldi_amd/aug.py `strong_views`: the reference's chain, three launches per batch).  Each yielded dict is a
+    shallow copy with `img_weak` = the device weak view and `image` = its strong view (`augs` None: the weak view itself, and
+    nothing is drawn).
+
+    The draws come from a private RandomState / random.Random seeded with `seed` (as detectron2 seeds each loader worker),
+    so the process's global streams are never touched.  It runs one batch ahead: batch k+1's host work (the inner loader,
+    the draws) on a background thread, its copies and launches on a side stream, while the caller runs step k; `next()`
+    only makes the caller's current stream wait for the batch (no host sync)."""
+
+    def __init__(self, loader, augs, seed: int, device=None):
+        self.loader, self.augs, self.seed, self.device = loader, augs, int(seed), device
+
+    def __iter__(self):
+        return _DeviceStrongAugIter(self)
+
+
+class _DeviceStrongAugIter:
+    def __init__(self, owner: DeviceStrongAugLoader):
+        self.it = iter(owner.loader)
+        self.augs = owner.augs
+        self.np_rng, self.py_rng = np.random.RandomState(owner.seed), random.Random(owner.seed)
+        self.device = torch.device(owner.device) if owner.device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.side = torch.cuda.Stream(self.device)
+        self.pool = ThreadPoolExecutor(1)
+        self.ready = self.future = None
+        self.done = False
+
+    def _prepare(self):
+        """host work (background thread): the inner loader's batch, pinned weak views, the draws in image order"""
+        from . import aug
+        batch = next(self.it)
+        weak, params = [], []
+        for rec in batch:
+            w = rec[WEAK_IMG_KEY]
+            if w.dtype != torch.uint8 or w.dim() != 3 or w.shape[0] != 3:
+                raise ValueError(f"DeviceStrongAugLoader: `{WEAK_IMG_KEY}` must be a uint8 (3, H, W) image")
+            weak.append(w.contiguous() if w.is_cuda else w.contiguous().pin_memory())
+            if self.augs is not None:
+                params.append(aug.draw_strong_params(self.augs, int(w.shape[1]), int(w.shape[2]), np_rng=self.np_rng, py_rng=self.py_rng))
+        return batch, weak, params
+
+    def _issue(self, prepared):
+        """device work (caller's thread): weak-view copies and the batch's launches on the side stream"""
+        from . import aug
+        batch, weak, params = prepared
+        if any(w.is_cuda for w in weak):
+            self.side.wait_stream(torch.cuda.current_stream(self.device))       # device weak views come from the caller's stream
+        with torch.cuda.device(self.device), torch.cuda.stream(self.side):
+            dweak = [w if w.is_cuda else w.to(self.device, non_blocking=True) for w in weak]
+            strong = aug.launch_strong_views(dweak, params, chw=True) if self.augs is not None else dweak
+            ev = torch.cuda.Event()
+            ev.record(self.side)
+        out = []
+        for rec, w, s in zip(batch, dweak, strong):
+            rec = dict(rec)
+            rec[WEAK_IMG_KEY], rec["image"] = w, s
+            out.append(rec)
+        return out, ev, [t for t in dweak + list(strong) if t.device.type == "cuda"]
+
+    def _submit(self):
+        self.future = self.pool.submit(self._prepare)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self.done:
+            raise StopIteration
+        if self.ready is None:
+            self.ready = self._issue(self._prepare())
+            self._submit()
+        out, ev, tensors = self.ready
+        try:
+            self.ready = self._issue(self.future.result())
+            self._submit()
+        except StopIteration:
+            self.done = True
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(ev)
+        for t in tensors:
+            t.record_stream(cur)                        # the caching allocator must not hand them out before the caller is done
+        return out
+
+    def __del__(self):
+        pool = getattr(self, "pool", None)
+        if pool is not None:
+            pool.shutdown(wait=False)

@@ -19,7 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import synthetic
-from .dataloader import SyntheticDetectionLoader, WeakStrongDataloader
+from .dataloader import DeviceStrongAugLoader, SyntheticDetectionLoader, WeakStrongDataloader, device_strong_seed
 from .distill import build_distiller
 from .ema import EMA
 from .model import build_aldi
@@ -892,6 +892,17 @@ class ALDITrainer(DefaultTrainer):
         fixed = bool(syn.get("FIXED", False))
         labeled_loader = SyntheticDetectionLoader(labeled_bs // world, h, w, K, 1000 + 17 * rank, True, fixed=fixed) if labeled_bs > 0 else None
         unlabeled_loader = SyntheticDetectionLoader(unlabeled_bs // world, h, w, K, 2000 + 17 * rank, False, fixed=fixed) if unlabeled_bs > 0 else None
+        if cfg.AUG.get("DEVICE_STRONG", False):
+            # strong views from the reference's chain on the device (aldi/trainer.py:224-236 include_strong_augs: only for a
+            # domain whose strong view the batch asks for), private draws seeded per rank and domain
+            from .aug import get_strong_augs
+            base = max(int(cfg.SEED), 0)
+            if labeled_loader is not None:
+                labeled_loader = DeviceStrongAugLoader(labeled_loader, get_strong_augs(cfg, True) if "labeled_strong" in contents else None,
+                                                       device_strong_seed(base, rank, True))
+            if unlabeled_loader is not None:
+                unlabeled_loader = DeviceStrongAugLoader(unlabeled_loader, get_strong_augs(cfg, False) if "unlabeled_strong" in contents else None,
+                                                         device_strong_seed(base, rank, False))
         return WeakStrongDataloader(labeled_loader, unlabeled_loader, batch_contents)
 
     def before_step(self):

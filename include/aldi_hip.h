@@ -507,6 +507,46 @@ int aldi_aug_mic(unsigned char* img, int H, int W, const unsigned char* mask, in
 /* HWC uint8 -> CHW uint8 (the layout `dataset_dict["image"]` has in the reference, aldi/dataloader.py). */
 int aldi_aug_hwc_to_chw(const unsigned char* in, unsigned char* out, int H, int W, aldi_stream_t stream);
 
+/* Batched strong views: N weak views of any sizes -> N strong views in at most three launches, driven by one table of
+ * aldi_aug_desc in device memory (uploaded once per batch).  The chain is build_strong_augmentation's (+ MIC), applied in
+ * its order: contrast -> brightness -> saturation (flag COLOUR), saturation with wg (flag GRAY), gaussian_filter over the
+ * three axes (flag BLUR, radius <= 8), the erase rects in order (a later one wins), the MIC mask; every op rounds as the
+ * per-op kernels above do, so the bytes equal theirs.  Parameters are drawn on the host (aldi_amd/aug.py
+ * draw_strong_params). */
+enum { ALDI_AUG_COLOUR = 1, ALDI_AUG_GRAY = 2, ALDI_AUG_BLUR = 4, ALDI_AUG_CHW_IN = 8, ALDI_AUG_CHW_OUT = 16 };
+enum { ALDI_AUG_HALO = 8 };                       /* largest blur radius of the fused kernel (sigma < 2.125) */
+typedef struct aldi_aug_desc {
+    const unsigned char* src;                     /* weak view, device, uint8 CHW or HWC (flag CHW_IN), contiguous */
+    unsigned char* dst;                           /* strong view, device, CHW or HWC (flag CHW_OUT) */
+    const unsigned char* mask;                    /* MIC block mask [mh][mw] (1 = keep), device; NULL: no MIC */
+    unsigned long long sum;                       /* exact byte sum of src for the contrast mean: zero on upload, aldi_aug_batch_sums adds */
+    double wc, wb, ws, wg;                        /* contrast / brightness / saturation weights; grayscale stage's saturation weight */
+    double taps[ALDI_AUG_HALO + 1];               /* gaussian taps w[0..radius], w[radius] the centre (scipy's float64 weights) */
+    long fill_off[3];                             /* erase k: offset of its h*w*3 fill bytes in the arena */
+    int H, W, flags, radius;
+    int rect[3][4];                               /* erase k: h0, w0, h, w */
+    int nerase, mh, mw;
+    int tile_begin;                               /* first tile of this image in aldi_aug_batch_view's grid (16 x 64 pixel tiles) */
+    int sum_begin, sum_blocks;                    /* blocks of this image in aldi_aug_batch_sums' grid (0 unless COLOUR) */
+} aldi_aug_desc;
+/* One segment of an erase fill: replays numpy's MT19937 stream from a snapshot (key[624] + pos, from aldi_np_mt_advance) and
+ * writes clip_u8((float)d * 255) for ndoubles consecutive random_sample() values d to arena[out_off ...]. */
+typedef struct aldi_aug_fill_job {
+    const unsigned int* snap;                     /* key[624], device */
+    long out_off;
+    int pos, ndoubles;
+} aldi_aug_fill_job;
+/* launch 1: desc[i].sum += the bytes of every image with sum_blocks > 0 (nblocks = sum of sum_blocks, 32 KiB per block) */
+int aldi_aug_batch_sums(aldi_aug_desc* desc, int n, int nblocks, aldi_stream_t stream);
+/* launch 2: one workgroup per job */
+int aldi_aug_batch_fills(const aldi_aug_fill_job* jobs, int njobs, unsigned char* arena, aldi_stream_t stream);
+/* launch 3: the fused strong view; ntiles = sum over images of ceil(H / 16) * ceil(W / 64) */
+int aldi_aug_batch_view(const aldi_aug_desc* desc, int n, int ntiles, const unsigned char* arena, aldi_stream_t stream);
+/* Host helper (no device work): numpy's legacy RandomState (key[624], *pos) advanced by n 32-bit outputs (random_sample
+ * takes two); the state at outputs 0, seg, 2 seg, ... < n goes to snaps[k][624] / snap_pos[k] (at most max_snaps; seg <= 0:
+ * none).  Equals get_state() after rand(n / 2) bit for bit. */
+int aldi_np_mt_advance(unsigned int* key, int* pos, long n, long seg, unsigned int* snaps, int* snap_pos, long max_snaps);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * ViTDet trunk (BASELINE cfg 4).  Replaces, for the ALDI step, the torch modules that
  * aldi/backbone.py:21-43 (checkpointed_vit_forward) drives: detectron2 modeling/backbone/vit.py Block / Attention /
