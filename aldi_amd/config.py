@@ -179,6 +179,9 @@ def add_aldi_config(cfg: CfgNode):
     # the strong views of the training loader from the reference's chain (get_strong_augs of the keys above), built on the
     # device in three launches per batch (aldi_amd/dataloader.py DeviceStrongAugLoader); off: the loader's own views
     _C.AUG.DEVICE_STRONG = False
+    # COCO box AP of `test()` matched and accumulated on the device (aldi_amd/evaluation.py DeviceCOCOEvaluator: the host
+    # evaluator's numbers, one device -> host copy per evaluation); off: Detectron2COCOEvaluatorAdapter on the host
+    _C.TEST.DEVICE_EVAL = False
 
     _C.EMA = CN()
     _C.EMA.ENABLED = False

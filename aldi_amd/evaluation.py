@@ -138,7 +138,11 @@ def coco_bbox_metrics(images: Sequence[dict], annotations: List[dict], detection
         for an, rng in AREA_RNG.items():
             per_img = [evaluate_img(dts.get((i, c), []), gts.get((i, c), []), rng, MAX_DETS[-1]) for i in img_ids]
             prec[c, an] = accumulate(per_img)
+    return summarize_bbox(prec, category_ids)
 
+
+def summarize_bbox(prec: Dict[tuple, Optional[tuple]], category_ids: Sequence[int]) -> "OrderedDict[str, float]":
+    """COCOeval.summarize's six box numbers from {(category, area name): (precision [T, R], recall [T]) or None}"""
     def summarize(area="all", iou=None):
         vals = []
         for c in category_ids:
@@ -211,6 +215,208 @@ class Detectron2COCOEvaluatorAdapter:
                     return OrderedDict()
         res = coco_bbox_metrics(self.images, [dict(a) for a in self.annotations], preds, list(range(self.num_classes)))
         return OrderedDict(bbox=res)
+
+
+def kernel_constants() -> Dict[str, np.ndarray]:
+    """what the device kernels are handed: the host's own doubles (area_rng [4, 2], iou_thrs [10], rec_thrs [101])"""
+    return dict(area_rng=np.array([r for r in AREA_RNG.values()], dtype=np.float64), iou_thrs=np.ascontiguousarray(IOU_THRS, dtype=np.float64),
+                rec_thrs=np.ascontiguousarray(REC_THRS, dtype=np.float64))
+
+
+def pack_ground_truth(images: Sequence[dict], annotations: List[dict], num_classes: int) -> Dict[str, np.ndarray]:
+    """The adapter's annotation list per (image, category) segment `image_index * num_classes + category` (CSR, annotation order
+    kept inside a segment): boxes [G, 4] XYWH, area [G] (after `maybe_add_optional_annotations`), flags [G] (bit 0 iscrowd,
+    bit 1 ignore), off [I * K + 1].  Annotations of an unknown image or category are never looked up by the host and are dropped."""
+    anns = [dict(a) for a in annotations]
+    maybe_add_optional_annotations(anns)
+    index = {}
+    for i, im in enumerate(images):
+        if im["id"] in index:
+            raise ValueError(f"image id {im['id']!r} occurs twice")
+        index[im["id"]] = i
+    K, nseg = num_classes, len(images) * num_classes
+    seg, rows = [], []
+    for a in anns:
+        c = a["category_id"]
+        if a["image_id"] in index and c in range(K):
+            seg.append(index[a["image_id"]] * K + int(c))
+            rows.append(a)
+    seg = np.array(seg, dtype=np.int64)
+    order = np.argsort(seg, kind="mergesort")
+    rows = [rows[i] for i in order]
+    return dict(boxes=np.array([a["bbox"] for a in rows], dtype=np.float64).reshape(-1, 4),
+                area=np.array([a["area"] for a in rows], dtype=np.float64),
+                flags=np.array([(1 if a["iscrowd"] else 0) | (2 if a.get("ignore", 0) else 0) for a in rows], dtype=np.uint8),
+                off=np.searchsorted(seg[order], np.arange(nseg + 1)).astype(np.int32))
+
+
+def merge_detection_shards(shards: Sequence[tuple]) -> tuple:
+    """Per-rank compact detections (boxes [n, 4] f64 XYWH, scores [n] f64, classes [n] i64, image index [n] i64, valid [n] bool),
+    in any gather order -> one set keyed by image: ordered by image index, each image's detections in the order its rank
+    produced them (what an unsharded run over the images in order holds)."""
+    import torch
+    cat = [torch.cat([s[k] for s in shards]) for k in range(5)]
+    order = torch.sort(cat[3], stable=True)[1]
+    return tuple(t[order] for t in cat)
+
+
+class DeviceCOCOEvaluator:
+    """`Detectron2COCOEvaluatorAdapter`'s interface and numbers with detections, matching and accumulation on the device
+    (csrc/eval.hip; `TEST.DEVICE_EVAL`).  `process` appends to a device arena and launches nothing that waits for the device;
+    `evaluate` runs the kernels and makes ONE device -> host copy (precision, recall, valid), which `summarize_bbox` turns into
+    the six numbers with the host's numpy expressions."""
+
+    def __init__(self, dataset_name: str, dataset_dicts: Sequence[dict], num_classes: int, output_dir: Optional[str] = None,
+                 distributed: bool = True, device=None):
+        import torch
+        from . import _lib as L
+        host = Detectron2COCOEvaluatorAdapter(dataset_name, dataset_dicts, num_classes, output_dir=output_dir, distributed=distributed)
+        self.dataset_name, self.output_dir, self.distributed, self.num_classes = dataset_name, output_dir, distributed, num_classes
+        self.images, self.annotations = host.images, host.annotations         # converted exactly as the adapter converts them
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._index = {im["id"]: i for i, im in enumerate(self.images)}
+        self._gt_host = pack_ground_truth(self.images, self.annotations, num_classes)
+        self._gt = {k: self._upload(v) for k, v in self._gt_host.items()}
+        self._const = {k: self._upload(v) for k, v in kernel_constants().items()}
+        nseg = len(self.images) * num_classes
+        self._seg_bounds = torch.arange(nseg + 2, device=self.device)
+        self._cat_bounds = torch.arange(num_classes + 1, device=self.device)
+        self._ws = torch.empty(int(L.lib.aldi_coco_match_workspace(len(self._gt_host["area"]))), dtype=torch.uint8, device=self.device)
+        self._dummy = torch.zeros(64, dtype=torch.uint8, device=self.device)
+        self._cap = 0
+        self.last = None
+        self.reset()
+
+    def _upload(self, a: np.ndarray):
+        """host array -> device through pinned memory (an asynchronous copy: nothing waits for the device)"""
+        import torch
+        t = torch.from_numpy(np.ascontiguousarray(a))
+        return t.pin_memory().to(self.device, non_blocking=True) if t.numel() else torch.empty(t.shape, dtype=t.dtype, device=self.device)
+
+    def _ptr(self, t):
+        return t.data_ptr() if t.numel() else self._dummy.data_ptr()
+
+    def reset(self):
+        self._n = 0
+        self._entries: List[tuple] = []          # per `process` entry: (sx, sy, width, height), image index, detections
+        self._entry_img: List[int] = []
+        self._entry_n: List[int] = []
+
+    def _reserve(self, n: int):
+        import torch
+        if self._n + n <= self._cap:
+            return
+        cap = max(2 * self._cap, self._n + n, 4096)
+        new = (torch.empty((cap, 4), dtype=torch.float32, device=self.device), torch.empty(cap, dtype=torch.float32, device=self.device),
+               torch.empty(cap, dtype=torch.int64, device=self.device))
+        if self._n:
+            for dst, src in zip(new, (self._boxes, self._scores, self._classes)):
+                dst[:self._n].copy_(src[:self._n])
+        self._boxes, self._scores, self._classes = new
+        self._cap = cap
+
+    def process(self, inputs: Sequence[dict], outputs: Sequence) -> None:
+        """as the adapter's `process`; the tensors stay on (or are uploaded to) the device, their lengths are host integers"""
+        for inp, out in zip(inputs, outputs):
+            inst = out["instances"] if isinstance(out, dict) else out
+            boxes = inst.pred_boxes.tensor.detach().float().reshape(-1, 4)
+            n = int(boxes.shape[0])
+            ih, iw = inst.image_size
+            self._entries.append((inp["width"] / iw, inp["height"] / ih, float(inp["width"]), float(inp["height"])))
+            self._entry_img.append(self._index.get(inp["image_id"], -1))
+            self._entry_n.append(n)
+            if n == 0:
+                continue
+            self._reserve(n)
+            s = slice(self._n, self._n + n)
+            self._boxes[s].copy_(boxes, non_blocking=True)
+            self._scores[s].copy_(inst.scores.detach().float().reshape(-1), non_blocking=True)
+            self._classes[s].copy_(inst.pred_classes.detach().reshape(-1), non_blocking=True)
+            self._n += n
+
+    def _compact(self):
+        """the arena through `aldi_coco_postprocess` -> (boxes XYWH f64, scores f64, classes, image index, valid)"""
+        import torch
+        from . import _lib as L, ops
+        n = self._n
+        counts = np.array(self._entry_n, dtype=np.int64)
+        entry = self._upload(np.repeat(np.arange(len(counts), dtype=np.int32), counts))
+        img = self._upload(np.repeat(np.array(self._entry_img, dtype=np.int64), counts))
+        meta = self._upload(np.array(self._entries, dtype=np.float64).reshape(-1, 4))
+        boxes = torch.empty((n, 4), dtype=torch.float64, device=self.device)
+        scores = torch.empty(n, dtype=torch.float64, device=self.device)
+        valid = torch.empty(n, dtype=torch.uint8, device=self.device)
+        classes = self._classes[:n] if n else torch.empty(0, dtype=torch.int64, device=self.device)
+        if n:
+            with torch.cuda.device(self.device):
+                L.call("aldi_coco_postprocess", self._boxes.data_ptr(), self._scores.data_ptr(), self._classes.data_ptr(), entry.data_ptr(),
+                       meta.data_ptr(), n, self.num_classes, boxes.data_ptr(), scores.data_ptr(), valid.data_ptr(), ops.stream_ptr())
+        return boxes, scores, classes, img, (valid != 0) & (img >= 0)
+
+    def _evaluate_device(self, arrays, mark=lambda stage: None):
+        """match + accumulate -> one device buffer [precision K*4*10*101 | recall K*4*10 | valid K*4 (int32)]; no host sync.
+        `mark(stage)` is called after each stage has been enqueued (tools/bench_eval.py records device events there)."""
+        import torch
+        from . import _lib as L, ops
+        boxes, scores, classes, img, valid = arrays
+        I, K, N = len(self.images), self.num_classes, int(scores.shape[0])
+        nseg = I * K
+        A, T, R = len(AREA_RNG), len(IOU_THRS), len(REC_THRS)
+        n_prec, n_rec = K * A * T * R, K * A * T
+        out = torch.zeros(n_prec + n_rec + (K * A + 1) // 2, dtype=torch.float64, device=self.device)
+        if nseg == 0:
+            return out
+        # (image, category) segments, each in stable descending score order; invalid slots go to a bucket past the last segment
+        key = torch.where(valid, img * K + classes, nseg)
+        o1 = torch.sort(scores, descending=True, stable=True)[1]
+        ks, o2 = torch.sort(key[o1], stable=True)
+        order = o1[o2]
+        sboxes, sscores = boxes[order].contiguous(), scores[order]
+        det_off = torch.searchsorted(ks, self._seg_bounds).to(torch.int32)
+        mark("segment_sorts")
+        mbits = torch.zeros(N, dtype=torch.int64, device=self.device)
+        igbits = torch.zeros(N, dtype=torch.int64, device=self.device)
+        num_gt = torch.empty(nseg * A, dtype=torch.int32, device=self.device)
+        g, c = self._gt, self._const
+        with torch.cuda.device(self.device):
+            L.call("aldi_coco_match", self._ptr(sboxes), det_off.data_ptr(), self._ptr(g["boxes"]), self._ptr(g["area"]), self._ptr(g["flags"]),
+                   g["off"].data_ptr(), nseg, int(g["area"].shape[0]), c["area_rng"].data_ptr(), c["iou_thrs"].data_ptr(), MAX_DETS[-1],
+                   self._ws.data_ptr(), self._ptr(mbits), self._ptr(igbits), num_gt.data_ptr(), ops.stream_ptr())
+        mark("match")
+        # per category: the slots that survived the cut, images in order, then the stable descending score order
+        rank = torch.arange(N, device=self.device) - det_off[ks].long()
+        key2 = torch.where((rank < MAX_DETS[-1]) & (ks < nseg), ks % K, K)
+        p1 = torch.sort(sscores, descending=True, stable=True)[1]
+        k2s, p2 = torch.sort(key2[p1], stable=True)
+        perm = p1[p2].contiguous()
+        cat_off = torch.searchsorted(k2s, self._cat_bounds).to(torch.int32)
+        mark("category_sorts")
+        with torch.cuda.device(self.device):
+            L.call("aldi_coco_accumulate", self._ptr(perm), cat_off.data_ptr(), self._ptr(mbits), self._ptr(igbits), num_gt.data_ptr(), I, K,
+                   c["rec_thrs"].data_ptr(), out.data_ptr(), out[n_prec:].data_ptr(), out[n_prec + n_rec:].data_ptr(), ops.stream_ptr())
+        mark("accumulate")
+        return out
+
+    def evaluate(self) -> "OrderedDict[str, dict]":
+        import torch
+        arrays = self._compact()
+        if self.distributed:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                gathered = [None] * dist.get_world_size()
+                dist.all_gather_object(gathered, tuple(t.cpu() for t in arrays))       # one collective, as the adapter's list
+                if dist.get_rank() != 0:
+                    return OrderedDict()
+                arrays = tuple(self._upload(t.numpy()) for t in merge_detection_shards(gathered))
+        host = self._evaluate_device(arrays).cpu()                                       # the one device -> host copy
+        K, A, T, R = self.num_classes, len(AREA_RNG), len(IOU_THRS), len(REC_THRS)
+        n_prec, n_rec = K * A * T * R, K * A * T
+        precision = host[:n_prec].numpy().reshape(K, A, T, R)
+        recall = host[n_prec:n_prec + n_rec].numpy().reshape(K, A, T)
+        valid = host[n_prec + n_rec:].view(torch.int32)[:K * A].numpy().reshape(K, A)
+        self.last = dict(precision=precision, recall=recall, valid=valid)
+        prec = {(c, an): (precision[c, ai], recall[c, ai]) if valid[c, ai] else None for c in range(K) for ai, an in enumerate(AREA_RNG)}
+        return OrderedDict(bbox=summarize_bbox(prec, list(range(K))))
 
 
 def inference_on_dataset(model, data_loader, evaluator) -> "OrderedDict[str, dict]":

@@ -21,6 +21,7 @@ backward launches the overlapped gradient exchange, reduce.BucketedReducer)."""
 from __future__ import annotations
 
 import contextlib
+import gc
 import os
 import time
 from types import SimpleNamespace
@@ -1047,7 +1048,18 @@ class FusedStep:
             if not hasattr(self, "_cap_stream"):      # behind the (long) workgroups of the weight-gradient stream
                 self._cap_stream = torch.cuda.Stream(device=self.eng.device, priority=prio)
             kw["stream"] = self._cap_stream
-        with torch.cuda.graph(g, pool=self.pool, capture_error_mode="thread_local", **kw):
-            out = fn()
+        # No cyclic collection may run inside the capture: finalizers of dead objects (an earlier trainer's graphs, events, stream-
+        # recorded or pinned buffers) issue HIP calls of their own, and the runtime aborts the process when one of them lands in a
+        # recording.  When a collection falls is a matter of allocation counts, so collect now, at a safe point (dead cycles
+        # also give their device memory back to the pool), and keep the collector off until the capture has ended.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, pool=self.pool, capture_error_mode="thread_local", **kw):
+                out = fn()
+        finally:
+            if gc_was_on:
+                gc.enable()
         self.stats["captures"] += 1
         return g, out

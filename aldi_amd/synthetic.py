@@ -134,3 +134,37 @@ def clone_batch(data):
             out.append([{"image": d["image"].clone(), "instances": {k: (v.clone() if isinstance(v, torch.Tensor) else v)
                                                                     for k, v in d["instances"].items()}} for d in part])
     return tuple(out)
+
+
+def make_eval_scene(num_images: int = 50, num_classes: int = 8, height: int = 1024, width: int = 2048, seed: int = 0, dets_per_image: int = 100):
+    """A validation set with detections for the evaluator tests and tools/bench_eval.py: per image 5-39 ground-truth boxes (5 %
+    crowd; small, medium and large ones), 80 % of them detected with +-20 % jitter, clutter up to exactly `dets_per_image`
+    detections, float32 scores rounded to two decimals (ties).  -> (records, detections): detectron2-format records and, per
+    image, dict(boxes [D, 4] XYXY float32, scores [D] float32, classes [D] int64) in the image's own pixels."""
+    import numpy as np
+    rng = np.random.RandomState(seed)
+    records, detections = [], []
+    for i in range(num_images):
+        anns, boxes, scores, classes = [], [], [], []
+        for _ in range(int(rng.randint(5, 40))):
+            w, h = np.exp(rng.uniform(np.log(10.0), np.log(420.0), 2))
+            x, y = rng.uniform(0, width - w), rng.uniform(0, height - h)
+            c = int(rng.randint(0, num_classes))
+            anns.append(dict(bbox=[float(x), float(y), float(w), float(h)], bbox_mode="XYWH_ABS", category_id=c, iscrowd=int(rng.rand() < 0.05),
+                             area=float(w * h)))
+            if rng.rand() < 0.8 and len(boxes) < dets_per_image:
+                j = rng.uniform(-0.2, 0.2, 4) * np.array([w, h, w, h])
+                boxes.append([x + j[0], y + j[1], x + j[0] + max(w + j[2], 2.0), y + j[1] + max(h + j[3], 2.0)])
+                scores.append(rng.uniform(0.3, 1.0))
+                classes.append(c if rng.rand() < 0.9 else int(rng.randint(0, num_classes)))
+        while len(boxes) < dets_per_image:
+            w, h = np.exp(rng.uniform(np.log(8.0), np.log(300.0), 2))
+            x, y = rng.uniform(0, width - w), rng.uniform(0, height - h)
+            boxes.append([x, y, x + w, y + h])
+            scores.append(rng.uniform(0.0, 0.7))
+            classes.append(int(rng.randint(0, num_classes)))
+        records.append(dict(image_id=i, height=height, width=width, annotations=anns))
+        detections.append(dict(boxes=torch.from_numpy(np.array(boxes, dtype=np.float32).reshape(-1, 4)),
+                               scores=torch.from_numpy(np.round(np.array(scores, dtype=np.float32), 2)),
+                               classes=torch.from_numpy(np.array(classes, dtype=np.int64))))
+    return records, detections

@@ -935,10 +935,12 @@ class ALDITrainer(DefaultTrainer):
 
     @classmethod
     def build_evaluator(cls, cfg, dataset_name, output_folder=None, dataset_dicts=None):
-        """Just do COCO Evaluation."""
-        from .evaluation import Detectron2COCOEvaluatorAdapter
+        """Just do COCO Evaluation (`TEST.DEVICE_EVAL`: matched and accumulated on the device, same numbers)."""
+        from .evaluation import Detectron2COCOEvaluatorAdapter, DeviceCOCOEvaluator
         if output_folder is None:
             output_folder = os.path.join(cfg.OUTPUT_DIR, "inference")
+        if cfg.TEST.get("DEVICE_EVAL", False):
+            return DeviceCOCOEvaluator(dataset_name, dataset_dicts or [], _num_classes(cfg), output_dir=output_folder)
         return Detectron2COCOEvaluatorAdapter(dataset_name, dataset_dicts or [], _num_classes(cfg), output_dir=output_folder)
 
     @classmethod

@@ -548,6 +548,35 @@ int aldi_aug_batch_view(const aldi_aug_desc* desc, int n, int ntiles, const unsi
 int aldi_np_mt_advance(unsigned int* key, int* pos, long n, long seg, unsigned int* snaps, int* snap_pos, long max_snaps);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * COCO box-AP evaluation (aldi_amd/evaluation.py DeviceCOCOEvaluator, `TEST.DEVICE_EVAL`): pycocotools' COCOeval for
+ * iouType="bbox" as the host evaluator states it (evaluate_img, accumulate), in fp64 with the host's operations in the
+ * host's order, so precision / recall are equal to the host's.  Area ranges, IoU and recall thresholds are passed in as
+ * the host's doubles (device pointers).  A "segment" is one (image, category): index image * num_classes + category.
+ * ------------------------------------------------------------------------------------------------------------------ */
+enum { ALDI_COCO_AREAS = 4, ALDI_COCO_THRS = 10, ALDI_COCO_RECS = 101 };
+/* detector_postprocess + XYXY -> XYWH of `process` for n detections: boxes [n][4] float32 XYXY in network pixels, entry[i] =
+ * row of meta [.][4] = {width / net_w, height / net_h, width, height} (doubles formed on the host); out_boxes [n][4] XYWH,
+ * out_scores [n], out_valid [n] = box non-empty after the clip and 0 <= class < num_classes. */
+int aldi_coco_postprocess(const float* boxes, const float* scores, const long* classes, const int* entry, const double* meta, long n,
+                          int num_classes, double* out_boxes, double* out_scores, unsigned char* out_valid, aldi_stream_t stream);
+/* bytes of aldi_coco_match's workspace for num_gt ground-truth boxes in all */
+size_t aldi_coco_match_workspace(long num_gt);
+/* evaluate_img for every segment.  det_boxes [N][4] XYWH grouped by segment and, inside one, in the stable descending score
+ * order (det_off [num_segments + 1]; only the first max_det <= 128 of a segment are matched); ground truth in annotation
+ * order per segment (gt_off [num_segments + 1]), gt_flags bit 0 = iscrowd, bit 1 = ignore, gt_area as the host formed it;
+ * area_rng [4][2], iou_thrs [10].  Per detection slot: bit (area * 10 + threshold) of matched / dt_ignore; num_gt_out
+ * [num_segments][4] = ground truth not ignored in that area range. */
+int aldi_coco_match(const double* det_boxes, const int* det_off, const double* gt_boxes, const double* gt_area, const unsigned char* gt_flags,
+                    const int* gt_off, int num_segments, long num_gt, const double* area_rng, const double* iou_thrs, int max_det,
+                    void* workspace, unsigned long long* matched, unsigned long long* dt_ignore, int* num_gt_out, aldi_stream_t stream);
+/* accumulate for every (category, area range, threshold).  perm [cat_off[c] .. cat_off[c + 1]) = the matched slots of
+ * category c in the host's order (images in order, then stable descending score); rec_thrs [101].  precision
+ * [K][4][10][101], recall [K][4][10], valid [K][4] (0 where the host returns None: no regular ground truth). */
+int aldi_coco_accumulate(const long* perm, const int* cat_off, const unsigned long long* matched, const unsigned long long* dt_ignore,
+                         const int* num_gt, int num_images, int num_classes, const double* rec_thrs, double* precision, double* recall,
+                         int* valid, aldi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * ViTDet trunk (BASELINE cfg 4).  Replaces, for the ALDI step, the torch modules that
  * aldi/backbone.py:21-43 (checkpointed_vit_forward) drives: detectron2 modeling/backbone/vit.py Block / Attention /
  * PatchEmbed and backbone/utils.py window_partition / get_rel_pos / get_abs_pos (detectron2 is not vendored in the
