@@ -358,9 +358,12 @@ def raise_on_error(code: int, who: str = "engine"):
     """decode an engine's device error word (RCNN.err; the kernels OR bits into it, nothing on the device stops)"""
     if code & 1:       # detectron2's find_top_rpn_proposals raises the same way
         raise FloatingPointError(f"{who}: predicted boxes or scores contain Inf/NaN. Training has diverged.")
-    if code & 2:
+    if code & 2:       # one bit, two writers: aldi_rpn_active_pixels (training) and aldi_detections (inference)
         raise RuntimeError(f"{who}: sparse RPN-head backward: more active pixels than (2 * BATCH_SIZE_PER_IMAGE + 4 * positives) per image; "
-                           "the excess was dropped, gradients of this step are wrong")
+                           "the excess was dropped, gradients of this step are wrong -- or, from the detection post-processing: a row of class "
+                           "scores contains Inf/NaN; the row was dropped")
+    if code & 4:
+        raise RuntimeError(f"{who}: detection post-processing: more than 8192 candidates above SCORE_THRESH_TEST in one image; the excess was dropped")
     if code & 8:
         raise RuntimeError(f"{who}: RPN top-k: the group barrier of `topk_fused_kernel` timed out (its workgroups were not co-resident); the candidates "
                            "of this step are wrong.  Set ALDI_RPN_TOPK_FUSED=0 for the five-launch path")

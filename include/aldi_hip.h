@@ -425,7 +425,9 @@ int aldi_box_losses_fused(const float* pred, int Cp, int K, const float* rois, c
 size_t aldi_detections_workspace(int N);
 /* fast_rcnn_inference + pseudo-label filter. pred fp32 [N*P][Cp] for all proposals.
  * det_* [N][topk], pl_* [N][pl_rows >= topk] (detections with score > pl_thresh, order kept, the rest of each row cleared: the
- * rows can be the ground-truth slots the matcher reads), counts [N]. */
+ * rows can be the ground-truth slots the matcher reads), counts [N].  err_flag |= 2 when a row's class scores are non-finite (the row
+ * is dropped, as detectron2 does in inference), |= 4 when an image has more than 8192 candidates above score_thresh (the excess is
+ * dropped, which ones is unspecified). */
 int aldi_detections(const float* pred, int Cp, int K, const float* props, const int* pcount, int P, int N, const int* img_hw,
                     const float* weights4, float score_thresh, float nms_thresh, int topk, float pl_thresh, void* workspace,
                     float* det_boxes, float* det_scores, int* det_cls, int* det_count,
