@@ -144,7 +144,8 @@ class Attention:
         bf = dict(dtype=torch.bfloat16, device=device)
         self.Qp = torch.empty((BH, self.L, self.Dq), **bf)
         self.Kp = torch.empty((BH, self.L, self.Dq), **bf)
-        self.KpT = torch.empty((BH, self.Dq, self.Lp), **bf)
+        # linear path: K'^T [Dq][Lp].  tiled path: k^T tile-major like VT, 64 x vt_cols, which exceeds Dq x Lp on thin grids (2 x 113)
+        self.KpT = torch.empty((BH, 64, vtc.value) if self.tiled else (BH, self.Dq, self.Lp), **bf)
         self.VT = torch.empty((BH, 64, vtc.value), **bf)
         self.QsT = torch.empty((BH, 64, self.Lp), **bf)
         self.dOT = torch.empty((BH, 64, self.Lp), **bf)

@@ -622,7 +622,7 @@ int aldi_adamw_step(float* p, const float* g, float* m, float* v, void* p_comput
 
 /* Attention with decomposed relative position bias, head dim 64, bf16.  nB = images x windows, each a gh x gw token grid
  * (L = gh*gw, Lp = L rounded up to 64); Dq from aldi_attn_layout (64 + gh + gw rounded up to 32 on small grids; 64 when rel_h == NULL),
- * at most 256.  Workspaces: Qp, Kp, dQp [nB*heads][L][Dq]; KpT [nB*heads][Dq][Lp]; VT [nB*heads][64][vt_cols]; QsT, dOT [nB*heads][64][Lp];
+ * at most 256.  Workspaces: Qp, Kp, dQp [nB*heads][L][Dq]; KpT [nB*heads][Dq][Lp] (tiled path: [nB*heads][64][vt_cols]); VT [nB*heads][64][vt_cols]; QsT, dOT [nB*heads][64][Lp];
  * lse, delta [nB*heads][L]. */
 typedef struct {
     const void* qkv;        /* [nB*L][3*heads*64]: q | k | v                                   */
