@@ -1263,6 +1263,33 @@ class RCNN:
         c.props, c.prop_count, c.pred_all = props, pcount, pred
         return c
 
+    # ------------------------------------------------------------------ feature-space diagnostic
+    def feature_pass(self, images, pooling: str = "avg"):
+        """One pooled vector per image and per proposal (the features the reference's tools/visualize_featurespace.py hooks out of the
+        backbone and the box pooler): -> (img [N][256] fp32: p6 pooled over the WHOLE staged canvas, prop [N * P][256] fp32: the 7x7
+        RoIAlign bins of every real proposal pooled, compacted image-major in proposal order -- rows past `total` are unwritten --,
+        total: device int32 [1]).  No box head, no detections, no host synchronisation."""
+        if type(self) is not RCNN:
+            raise ValueError(f"feature_pass: only the R50-FPN engine is supported, not {type(self).__name__}")
+        st, sizes, hw = self.stage_images(images)
+        c = self.trunk(st, sizes, save=False)
+        self.rpn_head(c, save=False)
+        N = st.shape[0]
+        shapes, geom, anchors = self.geometry(st.shape[2], st.shape[3])
+        props, _, pcount = self.proposals(c, geom, anchors, hw, N, training=False)
+        P = props.shape[1]
+        rois = torch.empty((N * P, 5), dtype=torch.float32, device=self.device)
+        ops.rois_from_proposals(props, pcount, P, N, rois)
+        pooled = torch.empty((N * P, POOL, POOL, FPN_C), dtype=self.dtype, device=self.device)
+        ops.roialign(self.roi_feats(c), rois, N * P, POOL, pooled, backward=False)
+        p6 = c.P[4]
+        img = torch.empty((N, FPN_C), dtype=torch.float32, device=self.device)
+        ops.pool_rows(p6.view(N, p6.shape[1] * p6.shape[2], FPN_C), img, pooling)
+        prop = torch.empty((N * P, FPN_C), dtype=torch.float32, device=self.device)
+        total = torch.empty((1,), dtype=torch.int32, device=self.device)
+        ops.pool_rows_counted(pooled.view(N, P, POOL * POOL, FPN_C), pcount, prop, total, pooling)
+        return img, prop, total
+
     # ------------------------------------------------------------------ backward
     def backward(self, c: Ctx, scales: Dict[str, float]):
         """Accumulate d(sum_k scales[k] * loss_k)/d(params) into weights.grad: loss gradients w.r.t. the

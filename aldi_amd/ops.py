@@ -602,3 +602,64 @@ def avgpool_bwd(gy: torch.Tensor, act: torch.Tensor) -> torch.Tensor:
     gx = torch.empty_like(act)
     L.call("aldi_avgpool_bwd", _p(gy), _p(act), _p(gx), N, H * W_, Cc, dtype_code(act.dtype), stream_ptr())
     return gx
+
+
+# ------------------------------------------------------------------------------- feature-space statistics (csrc/featstat.hip)
+POOL_MODES = {"avg": 0, "max": 1}
+
+
+def _pool_mode(mode: str) -> int:
+    if mode not in POOL_MODES:
+        raise ValueError(f"pooling must be one of {sorted(POOL_MODES)}, got {mode!r}")
+    return POOL_MODES[mode]
+
+
+def pool_rows(x: torch.Tensor, out: torch.Tensor, mode: str = "avg", row_off: int = 0) -> torch.Tensor:
+    """x [rows][S][C] (bf16 / fp32) -> out[row_off + r] = mean / max over S (fp32 [>= row_off + rows][C])"""
+    rows, S, Cc = x.shape
+    assert x.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32 and out.shape[1] == Cc, (x.shape, out.shape, out.dtype)
+    L.call("aldi_pool_rows", _p(x), rows, S, Cc, dtype_code(x.dtype), _pool_mode(mode), _p(out), row_off, out.shape[0], stream_ptr())
+    return out
+
+
+def pool_rows_counted(x: torch.Tensor, count: torch.Tensor, out: torch.Tensor, total: torch.Tensor, mode: str = "avg", row_off: int = 0) -> torch.Tensor:
+    """x [N][P][S][C] with device int32 count [N]: the rows p < count[n] pooled and written compacted (image-major) from out[row_off];
+    total (device int32 [1]) = their number; nothing else of `out` is written, nothing waits for the device"""
+    N, P, S, Cc = x.shape
+    assert x.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32 and out.shape[1] == Cc, (x.shape, out.shape, out.dtype)
+    assert count.dtype == torch.int32 and count.numel() == N and total.dtype == torch.int32, (count.dtype, count.shape, total.dtype)
+    L.call("aldi_pool_rows_counted", _p(x), N, P, S, Cc, dtype_code(x.dtype), _pool_mode(mode), _p(count), _p(out), row_off, out.shape[0], _p(total),
+           stream_ptr())
+    return out
+
+
+def moments_workspace(Cc: int, device) -> torch.Tensor:
+    return torch.empty(max(int(L.lib.aldi_moments_workspace(Cc)), 16), dtype=torch.uint8, device=device)
+
+
+def moments_accum(X: torch.Tensor, sum_: torch.Tensor, gram: torch.Tensor, count: torch.Tensor, workspace: torch.Tensor,
+                  n: Optional[int] = None, n_dev: Optional[torch.Tensor] = None) -> None:
+    """count += n, sum_ [C] += column sums, gram [C][C] += X^T X of the first n rows of X [cap][C] fp32 (fp64 device accumulators, ordered
+    reduction).  n: host int (default: every row of X), or n_dev: a device int32 word (the compacted total of pool_rows_counted)"""
+    cap, Cc = X.shape
+    assert X.is_contiguous() and X.dtype == torch.float32, (X.dtype,)
+    assert sum_.dtype == gram.dtype == count.dtype == torch.float64 and sum_.numel() == Cc and gram.numel() == Cc * Cc and gram.is_contiguous()
+    assert workspace.numel() >= int(L.lib.aldi_moments_workspace(Cc))
+    if n_dev is not None:
+        assert n is None and n_dev.dtype == torch.int32
+        L.call("aldi_moments_accum", _p(X), 0, _p(n_dev), cap, Cc, _p(sum_), _p(gram), _p(count), _p(workspace), stream_ptr())
+    else:
+        n = cap if n is None else int(n)
+        assert 0 <= n <= cap
+        L.call("aldi_moments_accum", _p(X), n, None, cap, Cc, _p(sum_), _p(gram), _p(count), _p(workspace), stream_ptr())
+
+
+def project2(X: torch.Tensor, mean: torch.Tensor, comp: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Y [n][2] fp32 = (X [n][C] fp32 - mean [C]) @ comp [2][C]^T, mean / comp fp64 on the device, fp64 accumulation"""
+    n, Cc = X.shape
+    assert X.is_contiguous() and X.dtype == torch.float32 and mean.dtype == comp.dtype == torch.float64
+    assert mean.numel() == Cc and tuple(comp.shape) == (2, Cc) and comp.is_contiguous() and mean.is_contiguous()
+    if out is None:
+        out = torch.empty((n, 2), dtype=torch.float32, device=X.device)
+    L.call("aldi_project2", _p(X), n, Cc, _p(mean), _p(comp), _p(out), stream_ptr())
+    return out

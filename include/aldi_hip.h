@@ -741,6 +741,32 @@ int aldi_scale_add(const void* x, const void* y, const float* gamma, const float
 int aldi_scale_add_backward(const void* g, const void* y, const float* gamma, const float* scale, void* dy, float* dgamma, long rows, int C,
                             int rows_per_sample, int dtype, aldi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Feature-space statistics (csrc/featstat.hip): the domain-gap diagnostic of the reference's tools/visualize_featurespace.py
+ * (one pooled vector per image / per proposal, 2-component PCA over source U target) without moving the pooled maps to the host.
+ * aldi_pool_rows: x [rows][S][C] (dtype, contiguous, C % 8 == 0) -> out[row_off + r][0..C) = mean (mode ALDI_POOL_AVG) or max
+ *   (ALDI_POOL_MAX; NaNs are ignored, as fmaxf does) over S, fp32 accumulation, always fp32.  Rows at or past out_rows are dropped.
+ * aldi_pool_rows_counted: x [N][P][S][C] with a DEVICE count [N] (clamped to [0, P]): row (n, p) is valid when p < count[n]; the valid
+ *   rows are written compacted -- image-major, in proposal order -- from out[row_off], the rest of `out` is not touched, invalid rows
+ *   of x are not read, and total[0] (device) = the number of valid rows.  No host synchronisation.
+ * aldi_moments_accum: X [n][C] fp32 (C % 8 == 0); count[0] += n, sum[c] += sum_i X[i][c], gram[a][b] += sum_i X[i][a] X[i][b]
+ *   (the FULL symmetric C x C matrix, row-major; kept bitwise symmetric), all fp64 device accumulators.  n_dev (nullable): a device int
+ *   that overrides n (clamped to [0, n_cap], the rows X holds; the grid is sized from n_cap).  No floating-point atomics: the rows are cut into
+ *   at most 32 fixed ranges (a function of n alone), every range's 64 x 64 partial tiles are summed row by row into `workspace`
+ *   (aldi_moments_workspace(C) bytes), and a second launch adds the ranges in order -- the same n and X give the same bits, and
+ *   n = 0 leaves the accumulators bit-unchanged.  Products of fp32 values are exact in fp64: the only error is the fp64 summation.
+ * aldi_project2: Y[i][k] = sum_c (X[i][c] - mean[c]) * comp[k][c], k in {0, 1}; mean [C] and comp [2][C] fp64, fp64 accumulation
+ *   in a fixed order, Y fp32 [n][2].
+ * ------------------------------------------------------------------------------------------------------------------ */
+enum { ALDI_POOL_AVG = 0, ALDI_POOL_MAX = 1 };
+int aldi_pool_rows(const void* x, long rows, int S, int C, int dtype, int mode, float* out, long row_off, long out_rows, aldi_stream_t stream);
+int aldi_pool_rows_counted(const void* x, int N, int P, int S, int C, int dtype, int mode, const int* count, float* out, long row_off,
+                           long out_rows, int* total, aldi_stream_t stream);
+size_t aldi_moments_workspace(int C);
+int aldi_moments_accum(const float* X, int n, const int* n_dev, int n_cap, int C, double* sum, double* gram, double* count, void* workspace,
+                       aldi_stream_t stream);
+int aldi_project2(const float* X, long n, int C, const double* mean, const double* comp, float* Y, aldi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
