@@ -92,6 +92,14 @@ def last_dispatch() -> str:
     return lib.aldi_last_dispatch().decode()
 
 
+def plan_dispatch(args, n: int = 1) -> str:
+    """aldi_conv_igemm_plan: the kernel variant aldi_conv_igemm (n == 1: args a ConvArgs) / aldi_conv_igemm_group (an array of n) would
+    choose under the current knobs -- nothing is launched, no GPU is needed and the pointers only have to be null or not"""
+    buf = C.create_string_buffer(224)
+    call("aldi_conv_igemm_plan", C.byref(args) if isinstance(args, C.Structure) else args, n, buf, len(buf))
+    return buf.value.decode()
+
+
 class BoxLossChunk(C.Structure):
     """aldi_box_loss_chunk (include/aldi_hip.h)"""
     _fields_ = [("r0", c_int), ("r1", c_int), ("grad_scale_cls", c_float), ("grad_scale_box", c_float), ("loss_box", c_void_p),

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/aldi_hip.h"
+#include "host.h"
 
 #define ALDI_CHECK_LAUNCH()                                   \
     do {                                                      \
@@ -12,19 +12,6 @@
     } while (0)
 
 int aldi_set_error(hipError_t e, const char* file, int line);
-int aldi_set_error_msg(int code, const char* msg);
-
-// run-time tuning knobs (aldi_set_tuning / ALDI_<NAME> environment defaults; core.hip)
-struct AldiTuning {
-    int igemm_xcd, igemm_tile, igemm_dbg, igemm_bigtile_min, igemm_bigtile_k, igemm_lintile_min, igemm_halo, igemm_force, igemm_group, igemm_k64_min, igemm_bigtile, igemm_narrow_k, igemm_splitk_tile, igemm_halo_f32, igemm_f32_tile64_max, igemm_direct, igemm_lean, igemm_halo64_mid, igemm_ws, igemm_ws_wgs, igemm_ws_min, igemm_halo_ilv, igemm_halo_small, igemm_halo96;
-    int wgrad_lean, wgrad_big_min, wgrad_big_slots, wgrad_slots, wgrad_xcd, wgrad_dma, wgrad_dbg, wgrad_group_slots, wgrad_group_epi, roialign_sep, roialign_bwd_rows, wgrad_db, wgrad_ordered, wgrad_big_group, wgrad_big_epi, wgrad_big_group_min, wgrad_lds_pad_kb, wgrad_f32_tile128, wgrad_dma64, wgrad_ilv, msda_gather, msda_gather_list, msda_bin, msda_bin_list;
-    int colsum_blocks, colsum_minrows, colsum_nt, colsum_block_kb;
-    int stem_mfma, sab_blocks, ln_bwd_blocks, ln_bwd_blocks_narrow, rpn_topk_fused, ema_blocks, nms_mask_tri, match_wave;
-};
-AldiTuning& aldi_tuning();
-void aldi_note_dispatch(const char* kernel);   // what aldi_last_dispatch() reports (thread local)
-
-typedef uint16_t bf16_t;  // raw bf16 storage
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;   // MFMA bf16 A/B fragment (4 VGPRs)
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;    // MFMA 16x16 accumulator / 16 B of fp32
@@ -109,5 +96,3 @@ __device__ __forceinline__ float block_sum(float v, float* smem /* >=16 floats *
     }
     return r;
 }
-
-static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

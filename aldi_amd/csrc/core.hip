@@ -31,66 +31,9 @@ extern "C" int aldi_noop(aldi_stream_t stream) {
 namespace {
 struct Knob { const char* name; int AldiTuning::*field; int dflt; };
 const Knob kKnobs[] = {
-    {"igemm_xcd", &AldiTuning::igemm_xcd, 1},
-    {"igemm_tile", &AldiTuning::igemm_tile, 0},
-    {"igemm_dbg", &AldiTuning::igemm_dbg, 0},
-    {"igemm_bigtile_min", &AldiTuning::igemm_bigtile_min, 1024},
-    {"igemm_bigtile", &AldiTuning::igemm_bigtile, 64},
-    {"igemm_bigtile_k", &AldiTuning::igemm_bigtile_k, 768},
-    {"igemm_lintile_min", &AldiTuning::igemm_lintile_min, 768},
-    {"igemm_halo", &AldiTuning::igemm_halo, 1},
-    {"igemm_force", &AldiTuning::igemm_force, 0},
-    {"igemm_k64_min", &AldiTuning::igemm_k64_min, 1024},
-    {"igemm_group", &AldiTuning::igemm_group, 1},
-    {"igemm_narrow_k", &AldiTuning::igemm_narrow_k, 512},
-    {"igemm_splitk_tile", &AldiTuning::igemm_splitk_tile, 2},
-    {"igemm_halo_f32", &AldiTuning::igemm_halo_f32, 0},
-    {"igemm_f32_tile64_max", &AldiTuning::igemm_f32_tile64_max, 4096},
-    {"igemm_direct", &AldiTuning::igemm_direct, 15},
-    {"igemm_lean", &AldiTuning::igemm_lean, 1},
-    {"igemm_halo64_mid", &AldiTuning::igemm_halo64_mid, 0},
-    {"igemm_ws", &AldiTuning::igemm_ws, 1},
-    {"igemm_ws_wgs", &AldiTuning::igemm_ws_wgs, 512},
-    {"igemm_ws_min", &AldiTuning::igemm_ws_min, 40000},
-    {"wgrad_lean", &AldiTuning::wgrad_lean, 1},
-    {"wgrad_big_min", &AldiTuning::wgrad_big_min, 28},
-    {"wgrad_big_slots", &AldiTuning::wgrad_big_slots, 256},
-    {"wgrad_slots", &AldiTuning::wgrad_slots, 384},
-    {"wgrad_xcd", &AldiTuning::wgrad_xcd, 1},
-    {"igemm_halo_ilv", &AldiTuning::igemm_halo_ilv, 1},
-    {"igemm_halo_small", &AldiTuning::igemm_halo_small, 0},
-    {"igemm_halo96", &AldiTuning::igemm_halo96, 0},
-    {"wgrad_dma", &AldiTuning::wgrad_dma, 0},
-    {"wgrad_dbg", &AldiTuning::wgrad_dbg, 0},
-    {"wgrad_group_slots", &AldiTuning::wgrad_group_slots, 0},
-    {"wgrad_group_epi", &AldiTuning::wgrad_group_epi, 24},
-    {"wgrad_db", &AldiTuning::wgrad_db, 0},
-    {"wgrad_ordered", &AldiTuning::wgrad_ordered, 1},
-    {"wgrad_big_group", &AldiTuning::wgrad_big_group, 1},
-    {"wgrad_big_epi", &AldiTuning::wgrad_big_epi, 12},
-    {"wgrad_big_group_min", &AldiTuning::wgrad_big_group_min, 64},
-    {"wgrad_lds_pad_kb", &AldiTuning::wgrad_lds_pad_kb, 0},
-    {"wgrad_f32_tile128", &AldiTuning::wgrad_f32_tile128, 1},
-    {"wgrad_dma64", &AldiTuning::wgrad_dma64, 3},
-    {"wgrad_ilv", &AldiTuning::wgrad_ilv, 0},
-    {"msda_gather", &AldiTuning::msda_gather, 7},
-    {"msda_gather_list", &AldiTuning::msda_gather_list, 1500},
-    {"msda_bin", &AldiTuning::msda_bin, 1},
-    {"msda_bin_list", &AldiTuning::msda_bin_list, 512},
-    {"roialign_sep", &AldiTuning::roialign_sep, 1},
-    {"roialign_bwd_rows", &AldiTuning::roialign_bwd_rows, 2},
-    {"colsum_blocks", &AldiTuning::colsum_blocks, 256},
-    {"colsum_minrows", &AldiTuning::colsum_minrows, 16},
-    {"colsum_nt", &AldiTuning::colsum_nt, 1024},
-    {"colsum_block_kb", &AldiTuning::colsum_block_kb, 384},
-    {"stem_mfma", &AldiTuning::stem_mfma, 1},
-    {"sab_blocks", &AldiTuning::sab_blocks, 512},
-    {"ln_bwd_blocks", &AldiTuning::ln_bwd_blocks, 512},
-    {"ln_bwd_blocks_narrow", &AldiTuning::ln_bwd_blocks_narrow, 1024},
-    {"rpn_topk_fused", &AldiTuning::rpn_topk_fused, 1},
-    {"ema_blocks", &AldiTuning::ema_blocks, 2048},
-    {"nms_mask_tri", &AldiTuning::nms_mask_tri, 1},
-    {"match_wave", &AldiTuning::match_wave, 1},
+#define ALDI_KNOB_ROW(name, dflt) {#name, &AldiTuning::name, dflt},
+    ALDI_KNOBS(ALDI_KNOB_ROW)
+#undef ALDI_KNOB_ROW
 };
 AldiTuning make_tuning() {
     AldiTuning t;

@@ -22,25 +22,11 @@
 // Replaces the cuDNN/MIOpen conv + FrozenBN + ReLU (+ residual) chain and torch Linear that
 // the reference reaches through detectron2 (aldi/align.py:72, aldi/distill.py:157,162).
 #include "common.h"
+#include "igemm_select.h"
 #include "tile_prims.h"
-#include <stdio.h>
 #include <stdlib.h>
 
 namespace {
-
-struct ConvDev {
-    const void* x; const void* w; void* y; float* y_f32;
-    const float* scale; const float* shift; const void* res; const void* mask;
-    int N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo;
-    int relu, res_mode, out_scale, OH, OW;
-    int M, K, xcd, dbg;
-    unsigned x_bytes, w_bytes;
-    int ksplit, slabs_per_split;     // split-K (plain 1x1 / linear): blockIdx.z = slice, slabs_per_split K slabs each
-    int lean;                        // plain 1x1 / linear with whole K slabs (direct-epilogue tiles): the K loop's DMA offsets are running sums
-    // ReLU masks as BITS (bf16, Cout % 8 == 0, plain output layout): [M][Cout / 8] bytes, bit c % 8 of byte c / 8 = (y[m][c] > 0).
-    // bits_out: written by the forward launch beside y; mask_bits: read by the backward launch instead of the 16x larger `mask` tensor.
-    const unsigned char* mask_bits; unsigned char* bits_out;
-};
 
 // ---- epilogue of a BM x BN tile: lane owns pixel (lane&15), channels (lane>>4)*4 .. +3 of each 16x16 accumulator fragment.
 // `stg`: the workgroup's LDS (LDS_BYTES of it), free for staging once every wave is past its last fragment read.
@@ -1053,17 +1039,6 @@ __global__ __launch_bounds__(512) void igemm_halo_rs_kernel(ConvDev p) {
     igemm_halo_rs_body<T, BN>(p, (int)(blockIdx.y * gridDim.x + blockIdx.x), (int)gridDim.x, (int)gridDim.y);
 }
 
-template <typename T, int BN>
-int launch_halo_rs(const ConvDev& d, hipStream_t st) {
-    dim3 grid(cdiv(d.M, 256), cdiv(d.Cout, BN));
-    hipLaunchKernelGGL((igemm_halo_rs_kernel<T, BN>), grid, dim3(512), 0, st, d);
-    ALDI_CHECK_LAUNCH();
-    char name[96];
-    snprintf(name, sizeof(name), "igemm<bf16,256,%d,4,2,roles,halo>", BN);
-    aldi_note_dispatch(name);
-    return ALDI_OK;
-}
-
 #include "igemm_halo64.h"
 #include "igemm_ws.h"
 
@@ -1074,17 +1049,6 @@ __global__ __launch_bounds__(WM* WN * 64, (min_waves_per_simd<BM, WM * WN * 64, 
     igemm_body<T, BM, BN, WM, WN, KC, PIPE, HALO, EPI, LEAN>(p, (int)(blockIdx.y * gridDim.x + blockIdx.x), (int)gridDim.x, (int)gridDim.y);
 }
 
-// Several problems of ONE layer shape in one launch -- the student's and the teacher's pass through the same layer (different
-// weights, different images), and the same kind of layer on the maps of several pyramid levels (the four FPN output convs, the
-// RPN conv on p2..p6: same channels and taps, different H x W): the launches' fixed costs (ramp-up, partial last wave of tiles,
-// dependent-launch gap: ~10 us per 3x3 layer at these sizes) are paid once, and the small problems' tiles fill the large one's tail.
-constexpr int kMaxConvGroup = 12;
-struct ConvGroup {
-    int n;
-    int wg_begin[kMaxConvGroup + 1];          // first workgroup of each problem (multiples of 8: the XCD-aware tile order assumes it)
-    int nmt[kMaxConvGroup], nnt[kMaxConvGroup];
-    ConvDev p[kMaxConvGroup];
-};
 template <typename T, int BM, int BN, int WM, int WN, int KC, bool PIPE, bool HALO = false>
 __global__ __launch_bounds__(WM* WN * 64, (min_waves_per_simd<BM, WM * WN * 64, HALO>())) void igemm_group_kernel(ConvGroup G) {
     const int bid = (int)blockIdx.x;
@@ -1096,8 +1060,6 @@ __global__ __launch_bounds__(WM* WN * 64, (min_waves_per_simd<BM, WM * WN * 64, 
     if (local >= G.nmt[i] * G.nnt[i]) return;  // alignment padding
     igemm_body<T, BM, BN, WM, WN, KC, PIPE, HALO>(G.p[i], local, G.nmt[i], G.nnt[i]);
 }
-
-static thread_local const ConvGroup* g_group = nullptr;      // set by aldi_conv_igemm_group around dispatch<T>()
 
 template <int BM, int BN, int WM, int WN, bool DIRECT, bool ILV = false>
 __global__ __launch_bounds__(WM* WN * 64) void igemm_halo64_group_kernel(ConvGroup G) {
@@ -1111,298 +1073,97 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_halo64_group_kernel(ConvGro
     igemm_halo64_body<BM, BN, WM, WN, DIRECT, ILV>(G.p[i], local, G.nmt[i], G.nnt[i]);
 }
 
-// the 128-byte-slab halo kernel (igemm_halo64.h), alone or over the problems of a group; the direct epilogue (igemm_direct bit 8) when every
-// problem's output is plain bf16 with at most scale / shift / ReLU
-inline bool halo64_direct_ok(const ConvDev& d) {
-    return d.y && !d.y_f32 && d.out_scale == 1 && (d.Cout & 7) == 0 && !d.mask && !d.mask_bits && !d.bits_out && !d.res_mode;
+// ---- launchers: one per form of IGEMM_TILES, all with the row's template list (what a form does not have is ignored).  Which one runs, and
+// with which modifiers, is select_tile's decision (igemm_select.h); nothing here looks at the shape or the knobs again.
+
+// a group's workgroup table for BM x BN tiles: first workgroup of each problem (rounded to 8), its tile grid, d's xcd / dbg; -> workgroups of the launch
+int group_table(ConvGroup& G, const int BM, const int BN, const ConvDev& d) {
+    int wg = 0;
+    for (int i = 0; i < G.n; ++i) {
+        G.p[i].xcd = d.xcd; G.p[i].dbg = d.dbg;
+        G.nmt[i] = cdiv(G.p[i].M, BM); G.nnt[i] = cdiv(G.p[i].Cout, BN);
+        G.wg_begin[i] = wg;
+        wg += (G.nmt[i] * G.nnt[i] + 7) / 8 * 8;
+    }
+    for (int i = G.n; i <= kMaxConvGroup; ++i) G.wg_begin[i] = wg;
+    return wg;
 }
-template <int BM, int BN, int WM, int WN>
-int launch_halo64(const ConvDev& d, hipStream_t st) {
-    char name[96];
+
+template <typename T, int BM, int BN, int WM, int WN, int KC, bool PIPE, bool HALO, int EPI>
+int launch_tile(const Choice& c, const ConvDev& d, const ConvGroup* g, hipStream_t st) {
     constexpr int NT = WM * WN * 64;
-    bool direct = (aldi_tuning().igemm_direct & 8) != 0;
-    // igemm_halo_ilv: the interleaved K loop (reads / DMA pieces between the MFMAs of a sub-phase; igemm_halo64.h) -- the 8-wave 256 x 256 tile
-    constexpr bool HAS_ILV = BM == 256 && BN == 256 && WM == 4 && WN == 2;
-    const bool ilv = HAS_ILV && aldi_tuning().igemm_halo_ilv != 0;
-    if (g_group) {
-        ConvGroup G = *g_group;
-        int wg = 0;
-        for (int i = 0; i < G.n; ++i) {
-            G.p[i].xcd = d.xcd; G.p[i].dbg = d.dbg;
-            G.nmt[i] = cdiv(G.p[i].M, BM); G.nnt[i] = cdiv(G.p[i].Cout, BN);
-            G.wg_begin[i] = wg;
-            wg += (G.nmt[i] * G.nnt[i] + 7) / 8 * 8;
-            direct = direct && halo64_direct_ok(G.p[i]);
+    if constexpr (EPI != 0) {           // the direct-epilogue tiles: single launches without split-K (select_tile's direct_ok)
+        const dim3 grid(cdiv(d.M, BM), cdiv(d.Cout, BN));
+        if constexpr (!HALO) {
+            if (c.lean) hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KC, PIPE, HALO, EPI, true>), grid, dim3(NT), 0, st, d);
         }
-        for (int i = G.n; i <= kMaxConvGroup; ++i) G.wg_begin[i] = wg;
-        if (ilv) {
-            if (direct) hipLaunchKernelGGL((igemm_halo64_group_kernel<BM, BN, WM, WN, true, HAS_ILV>), dim3(wg), dim3(NT), 0, st, G);
+        if (HALO || !c.lean) hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KC, PIPE, HALO, EPI, false>), grid, dim3(NT), 0, st, d);
+    } else if (g) {
+        ConvGroup G = *g;
+        const int wg = group_table(G, BM, BN, d);
+        hipLaunchKernelGGL((igemm_group_kernel<T, BM, BN, WM, WN, KC, PIPE, HALO>), dim3(wg), dim3(NT), 0, st, G);
+    } else {
+        const dim3 grid(cdiv(d.M, BM), cdiv(d.Cout, BN), d.ksplit > 1 ? d.ksplit : 1);
+        hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KC, PIPE, HALO>), grid, dim3(NT), 0, st, d);
+    }
+    ALDI_CHECK_LAUNCH();
+    return ALDI_OK;
+}
+template <typename T, int BM, int BN, int WM, int WN, int KC, bool PIPE, int EPI>
+int launch_TAP(const Choice& c, const ConvDev& d, const ConvGroup* g, hipStream_t st) { return launch_tile<T, BM, BN, WM, WN, KC, PIPE, false, EPI>(c, d, g, st); }
+template <typename T, int BM, int BN, int WM, int WN, int KC, bool PIPE, int EPI>
+int launch_HALO(const Choice& c, const ConvDev& d, const ConvGroup* g, hipStream_t st) { return launch_tile<T, BM, BN, WM, WN, KC, PIPE, true, EPI>(c, d, g, st); }
+
+template <typename T, int BM, int BN, int WM, int WN, int KC, bool PIPE, int EPI>
+int launch_ROLES(const Choice&, const ConvDev& d, const ConvGroup*, hipStream_t st) {
+    static_assert(BM == 256 && WM * WN * 64 == 512, "igemm_halo_rs_body: 256 pixels on eight waves");
+    const dim3 grid(cdiv(d.M, BM), cdiv(d.Cout, BN));
+    hipLaunchKernelGGL((igemm_halo_rs_kernel<T, BN>), grid, dim3(512), 0, st, d);
+    ALDI_CHECK_LAUNCH();
+    return ALDI_OK;
+}
+
+// the 128-byte-slab halo kernel (igemm_halo64.h), alone or over the problems of a group
+template <typename T, int BM, int BN, int WM, int WN, int KC, bool PIPE, int EPI>
+int launch_HALO64(const Choice& c, const ConvDev& d, const ConvGroup* g, hipStream_t st) {
+    constexpr int NT = WM * WN * 64;
+    constexpr bool HAS_ILV = BM == 256 && BN == 256 && WM == 4 && WN == 2;       // (c.ilv is set for this tile only)
+    if (g) {
+        ConvGroup G = *g;
+        const int wg = group_table(G, BM, BN, d);
+        if (c.ilv) {
+            if (c.direct) hipLaunchKernelGGL((igemm_halo64_group_kernel<BM, BN, WM, WN, true, HAS_ILV>), dim3(wg), dim3(NT), 0, st, G);
             else hipLaunchKernelGGL((igemm_halo64_group_kernel<BM, BN, WM, WN, false, HAS_ILV>), dim3(wg), dim3(NT), 0, st, G);
         } else {
-            if (direct) hipLaunchKernelGGL((igemm_halo64_group_kernel<BM, BN, WM, WN, true>), dim3(wg), dim3(NT), 0, st, G);
+            if (c.direct) hipLaunchKernelGGL((igemm_halo64_group_kernel<BM, BN, WM, WN, true>), dim3(wg), dim3(NT), 0, st, G);
             else hipLaunchKernelGGL((igemm_halo64_group_kernel<BM, BN, WM, WN, false>), dim3(wg), dim3(NT), 0, st, G);
         }
-        ALDI_CHECK_LAUNCH();
-        snprintf(name, sizeof(name), "igemm_group%d<bf16,%d,%d,%d,%d,halo64%s%s>", G.n, BM, BN, WM, WN, direct ? ",direct" : "", (HAS_ILV && !ilv) ? ",lockstep" : "");
     } else {
-        direct = direct && halo64_direct_ok(d);
-        dim3 grid(cdiv(d.M, BM), cdiv(d.Cout, BN));
-        if (ilv) {
-            if (direct) hipLaunchKernelGGL((igemm_halo64_kernel<BM, BN, WM, WN, true, HAS_ILV>), grid, dim3(NT), 0, st, d);
+        const dim3 grid(cdiv(d.M, BM), cdiv(d.Cout, BN));
+        if (c.ilv) {
+            if (c.direct) hipLaunchKernelGGL((igemm_halo64_kernel<BM, BN, WM, WN, true, HAS_ILV>), grid, dim3(NT), 0, st, d);
             else hipLaunchKernelGGL((igemm_halo64_kernel<BM, BN, WM, WN, false, HAS_ILV>), grid, dim3(NT), 0, st, d);
         } else {
-            if (direct) hipLaunchKernelGGL((igemm_halo64_kernel<BM, BN, WM, WN, true>), grid, dim3(NT), 0, st, d);
+            if (c.direct) hipLaunchKernelGGL((igemm_halo64_kernel<BM, BN, WM, WN, true>), grid, dim3(NT), 0, st, d);
             else hipLaunchKernelGGL((igemm_halo64_kernel<BM, BN, WM, WN, false>), grid, dim3(NT), 0, st, d);
         }
-        ALDI_CHECK_LAUNCH();
-        snprintf(name, sizeof(name), "igemm<bf16,%d,%d,%d,%d,halo64%s%s>", BM, BN, WM, WN, direct ? ",direct" : "", (HAS_ILV && !ilv) ? ",lockstep" : "");
     }
-    aldi_note_dispatch(name);
-    return ALDI_OK;
-}
-
-template <typename T, int BM, int BN, int WM, int WN, int KC, bool PIPE = true, bool HALO = false, int EPI = 0>
-int launch(const ConvDev& d, hipStream_t st) {
-    if constexpr (EPI != 0) {
-        if (!g_group && d.ksplit <= 1) {
-            dim3 grid(cdiv(d.M, BM), cdiv(d.Cout, BN));
-            bool lean = false;
-            if constexpr (!HALO) lean = d.lean != 0;
-            if constexpr (!HALO) {
-                if (lean) hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KC, PIPE, HALO, EPI, true>), grid, dim3(WM * WN * 64), 0, st, d);
-            }
-            if (!lean) hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KC, PIPE, HALO, EPI, false>), grid, dim3(WM * WN * 64), 0, st, d);
-            ALDI_CHECK_LAUNCH();
-            char name[112];
-            snprintf(name, sizeof(name), "igemm<%s,%d,%d,%d,%d,%s,%s%s,%s>", "bf16", BM, BN, WM, WN, PIPE ? "pipe" : "flat", HALO ? "halo" : "tap", KC == 8 ? ",k64" : "",
-                     EPI == 2 ? "direct+res" : "direct");
-            aldi_note_dispatch(name);
-            return ALDI_OK;
-        }
-        return launch<T, BM, BN, WM, WN, KC, PIPE, HALO, 0>(d, st);
-    }
-    if (g_group) {
-        ConvGroup G = *g_group;
-        int wg = 0;
-        for (int i = 0; i < G.n; ++i) {
-            G.p[i].xcd = d.xcd; G.p[i].dbg = d.dbg;
-            G.nmt[i] = cdiv(G.p[i].M, BM); G.nnt[i] = cdiv(G.p[i].Cout, BN);
-            G.wg_begin[i] = wg;
-            wg += (G.nmt[i] * G.nnt[i] + 7) / 8 * 8;
-        }
-        for (int i = G.n; i <= kMaxConvGroup; ++i) G.wg_begin[i] = wg;
-        hipLaunchKernelGGL((igemm_group_kernel<T, BM, BN, WM, WN, KC, PIPE, HALO>), dim3(wg), dim3(WM * WN * 64), 0, st, G);
-        ALDI_CHECK_LAUNCH();
-        char name[112];
-        snprintf(name, sizeof(name), "igemm_group%d<%s,%d,%d,%d,%d,%s,%s%s>", G.n, sizeof(T) == 2 ? "bf16" : "f32", BM, BN, WM, WN, PIPE ? "pipe" : "flat", HALO ? "halo" : "tap",
-                 KC == 8 ? ",k64" : "");
-        aldi_note_dispatch(name);
-        return ALDI_OK;
-    }
-    dim3 grid(cdiv(d.M, BM), cdiv(d.Cout, BN), d.ksplit > 1 ? d.ksplit : 1);
-    hipLaunchKernelGGL((igemm_kernel<T, BM, BN, WM, WN, KC, PIPE, HALO>), grid, dim3(WM * WN * 64), 0, st, d);
     ALDI_CHECK_LAUNCH();
-    char name[112];
-    snprintf(name, sizeof(name), "igemm<%s,%d,%d,%d,%d,%s,%s%s>%s", sizeof(T) == 2 ? "bf16" : "f32", BM, BN, WM, WN, PIPE ? "pipe" : "flat", HALO ? "halo" : "tap",
-             KC == 8 ? ",k64" : "", d.ksplit > 1 ? " splitk" : "");
-    aldi_note_dispatch(name);
     return ALDI_OK;
 }
 
-// Tile selection.  Every arm is reachable from a test through aldi_set_tuning("igemm_force", ...) and named by
-// aldi_last_dispatch(); the thresholds are knobs of the same table (include/aldi_hip.h).
-template <typename T>
-int dispatch(ConvDev& d, hipStream_t st) {
-    const AldiTuning& tn = aldi_tuning();
-    d.xcd = tn.igemm_xcd;
-    d.dbg = tn.igemm_dbg;
-    // the N=2 micro-batch leaves the deep layers (res4/res5, FC heads) with far fewer 128x128 tiles than the
-    // 256 CUs: fall back to 64x64 tiles (4x the workgroups) when the big tiling cannot fill the chip
-    const long big = (long)cdiv(d.M, 128) * cdiv(d.Cout, 128);
-    // igemm_bigtile_min: long-K convs with thousands of tiles are bound by the L2 -> CU path (~31 B/clk/CU measured): the
-    // 256x128 tile (8 waves) moves 25 % fewer bytes per flop.
-    // igemm_bigtile_k / igemm_lintile_min: plain token GEMMs (ViT / ConvNeXt linears: K >= 768, M in the thousands): the
-    // 256x128 tile already pays from ~770 tiles on (+10 % at K = 768, +30 % at K = 3072 measured); the short-K 1x1 convs of
-    // the R50 trunk are HBM-bound and stay on 128x128.
-    // igemm_halo: 3x3 / stride 1 / pad 1 (every 3x3 of the network): halo form, the pixel tile is loaded once per three taps.
-    const int force = tn.igemm_force;     // 0 = heuristics; 1 = 128x128, 2 = 128x64, 3 = 64x64, 4 = 256x128, 5 = 128x16
-    // igemm_direct (bit mask: 1 = the 128x64 1x1 / tap tile, 2 = the 64x64 long-K tile, 4 = the 128x64 halo tile): the direct epilogue of
-    // the 64-channel tiles (igemm_epilogue_direct) for bf16 outputs in the plain layout; a residual needs the tile that prefetches it
-    const bool direct_ok = sizeof(T) == 2 && !g_group && d.y && !d.y_f32 && d.out_scale == 1 && (d.Cout & 7) == 0 && !d.mask && d.ksplit <= 1 &&
-                           !(d.mask_bits && (d.scale || d.shift)) && d.Cout >= 64 &&
-                           !(d.mask_bits && (d.Cout & 31));        // (the mask bits arrive by a 4-byte LDS-DMA at bit offset (m * Cout + ch): dword-aligned for Cout % 32 == 0 only)
-    const int direct = direct_ok ? tn.igemm_direct : 0;
-    d.lean = tn.igemm_lean && d.KH * d.KW == 1 && d.stride == 1 && d.pad == 0 && d.K % 64 == 0 && !(d.dbg & (8 | 16)) ? 1 : 0;
-    {
-        // (fp32 -- the parity mode and the Deformable-DETR step's trunk: the halo form is the same code, 16 channels per group; igemm_halo_f32)
-        const bool same3 = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 && d.Ho == d.H && d.Wo == d.W && d.Cin % 32 == 0 && d.out_scale == 1;
-        // fp32: OFF by default (igemm_halo_f32 = 0).  From ~400 half-width tiles on the halo form is faster alone (tools/halo_f32_sweep.py:
-        // 33 600 px x 256 -> 256 324 -> 228 us, 33 600 x 128 -> 128 162 -> 115; below, the 64 x 64 tap form's four-fold workgroup count wins:
-        // 8400 x 256 -> 256 148 vs 158, 2100 x 2048 -> 256 488 vs 647), but it sums K in another order (kh, channels, kw) than the tap form, so
-        // a layer would round differently at N = 2 and at N = 6 -- the parity mode's fused-vs-sequential comparison flips discrete decisions --
-        // and the Deformable-DETR step (N = 2 maps, few eligible layers) did not move (138 vs 140 ms)
-        const bool f32_halo = sizeof(T) == 4 && tn.igemm_halo_f32 > 0 && (long)cdiv(d.M, 128) * cdiv(d.Cout, 64) >= tn.igemm_halo_f32;
-        if (tn.igemm_halo && (sizeof(T) == 2 || f32_halo) && same3) {
-            if (force == 1) return launch<T, 128, 128, 2, 2, 4, false, true>(d, st);
-            if constexpr (sizeof(T) == 2)
-                if (force == 2 && (direct & 4) && !d.res_mode) return launch<T, 128, 64, 4, 1, 4, false, true, 1>(d, st);
-            if (force == 2) return launch<T, 128, 64, 4, 1, 4, false, true>(d, st);
-            if (force == 4) return launch<T, 256, 128, 4, 2, 4, false, true>(d, st);
-            if constexpr (sizeof(T) == 2) {
-                // 64 x 64 halo tiles (4 waves of 32 x 32): four times the workgroups of the 128 x 128 count -- for the layers whose 128 x 64 tile count sits just
-                // above a multiple of the 256 CUs (tools/quant_probe.py: 508 -> 516 workgroups = +23 % time)
-                // 96 x 64 halo tiles on THREE waves (32 x 64 per wave, as in the 128 x 64 tile): 4/3 of its workgroups -- tools/quant_probe.py: a CU runs three
-                // 128 x 64 workgroups in 1.23 x the time of two, and the mid-size layers of this network give it 2.06 (528 tiles) or 1.03 (264)
-                if (force == 17 && (direct & 4) && !d.res_mode) return launch<T, 96, 64, 3, 1, 4, false, true, 1>(d, st);
-                if (force == 17) return launch<T, 96, 64, 3, 1, 4, false, true>(d, st);
-                if (force == 16 && (direct & 4) && !d.res_mode) return launch<T, 64, 64, 2, 2, 4, false, true, 1>(d, st);
-                if (force == 16) return launch<T, 64, 64, 2, 2, 4, false, true>(d, st);
-                if (force == 9) return launch<T, 240, 128, 3, 2, 4, false, true>(d, st);
-                if (force == 10 && !g_group) return launch_halo_rs<T, 128>(d, st);
-                if (force == 11 && d.Cin % 64 == 0) return launch_halo64<256, 256, 4, 2>(d, st);
-                if (force == 13 && d.Cin % 64 == 0) return launch_halo64<128, 128, 2, 2>(d, st);
-                if (force == 15 && d.Cin % 64 == 0) return launch_halo64<256, 256, 2, 2>(d, st);
-            }
-            if (force == 0 || force == 3) {      // (no 64x64 halo form; 5 = the 128x16 tap form)
-                if (d.Cout <= 64) return launch<T, 128, 64, 4, 1, 4, false, true>(d, st);
-                if (big >= tn.igemm_bigtile_min) {
-                    // igemm_bigtile 64: 128-byte K slabs on a 256 x 256 tile (igemm_halo64.h) where the channels fill it
-                    if constexpr (sizeof(T) == 2)
-                        if (tn.igemm_bigtile == 64 && d.Cin % 64 == 0 && d.Cout % 256 == 0) return launch_halo64<256, 256, 4, 2>(d, st);
-                    if constexpr (sizeof(T) == 2)
-                        if (tn.igemm_bigtile == 65 && d.Cin % 64 == 0 && d.Cout % 256 == 0) return launch_halo64<256, 256, 2, 2>(d, st);
-                    if (tn.igemm_bigtile == 1) return launch<T, 128, 128, 2, 2, 4, false, true>(d, st);
-                    if constexpr (sizeof(T) == 2)
-                        if (tn.igemm_bigtile == 10 && !g_group) return launch_halo_rs<T, 128>(d, st);
-                    return launch<T, 256, 128, 4, 2, 4, false, true>(d, st);
-                }
-                // igemm_halo64_mid: mid-size layers with at least this many 128 x 128 tiles (two workgroups per CU: res3 / res4 conv2 at N = 4,
-                // res3 at N = 2) take that tile with 128-byte K slabs (igemm_halo64.h); 0 = never
-                if constexpr (sizeof(T) == 2)
-                    if (tn.igemm_halo64_mid > 0 && big >= tn.igemm_halo64_mid && d.Cin % 64 == 0 && d.Cout % 128 == 0) return launch_halo64<128, 128, 2, 2>(d, st);
-                // below ~1000 128x128 tiles the tile count of this network sits just above a multiple of the 256 CUs (16800 pixels =
-                // 131.25 row tiles: 264 / 528 tiles) and the last partial round costs as much as a full one; half-width tiles halve that
-                // tail (measured 8-25 % faster on every res3..res5 / FPN p3..p6 3x3 at N = 2 and 4)
-                // igemm_halo_small: long-K layers that do not even give every CU one or two 128 x 64 tiles (res5 conv2: 264 tiles at N = 4, 136 at N = 2)
-                // take 64 x 64 tiles -- four waves of 32 x 32, four times the workgroups per pixel: 32.9 -> 30.4 / 27.7 -> 24.3 us, bit-identical (same K order;
-                // tools/quant_probe.py, profiles/r06_quant_probe.txt).  At res4's K (16 800 px: 528 tiles) and res3's the larger tile wins (31.6 vs 38.3 us).
-                // OFF by default (0; 320 selects res5 conv2): in the step, beside the other stream's workgroups, it measured 0.5 % slower (8.07 vs 8.02 ms).
-                // igemm_halo96: layers with 200 .. 600 tiles of 128 x 64 (one or two per CU and a few left over: res4 conv2 at both batch sizes, res5 / res3 conv2
-                // at one of them) on 96 x 64 three-wave tiles: 2-6 % faster alone, bit-identical (profiles/r06_quant_probe.txt)
-                if constexpr (sizeof(T) == 2)
-                    if (tn.igemm_halo96 > 0) {
-                        const long t64 = (long)cdiv(d.M, 128) * cdiv(d.Cout, 64);
-                        if (t64 >= 200 && t64 <= 600) {
-                            if ((direct & 4) && !d.res_mode) return launch<T, 96, 64, 3, 1, 4, false, true, 1>(d, st);
-                            return launch<T, 96, 64, 3, 1, 4, false, true>(d, st);
-                        }
-                    }
-                if constexpr (sizeof(T) == 2)
-                    if (tn.igemm_halo_small > 0 && (long)cdiv(d.M, 128) * cdiv(d.Cout, 64) <= tn.igemm_halo_small && d.Cin >= 512) {
-                        if ((direct & 4) && !d.res_mode) return launch<T, 64, 64, 2, 2, 4, false, true, 1>(d, st);
-                        return launch<T, 64, 64, 2, 2, 4, false, true>(d, st);
-                    }
-                if constexpr (sizeof(T) == 2)
-                    if ((direct & 4) && !d.res_mode) return launch<T, 128, 64, 4, 1, 4, false, true, 1>(d, st);
-                return launch<T, 128, 64, 4, 1, 4, false, true>(d, st);
-            }
-        }
+// the launch table: one case per row of IGEMM_TILES
+int launch_choice(const Choice& c, const ConvDev& d, const ConvGroup* g, hipStream_t st) {
+    switch (c.tile) {
+#define IGEMM_TILE_CASE(id, T, form, BM, BN, WM, WN, KC, PIPE, EPI) \
+    case id: return launch_##form<T, BM, BN, WM, WN, KC, PIPE != 0, EPI>(c, d, g, st);
+        IGEMM_TILES(IGEMM_TILE_CASE)
+#undef IGEMM_TILE_CASE
+    default: break;
     }
-    // igemm_ws: the short-K 1x1 layers of the trunk (bottleneck expansions / reductions, their data gradients) on the weight-stationary persistent
-    // kernel (igemm_ws.h; its epilogue is the direct one: igemm_direct bit 1 turns it off with that); igemm_force 14 forces it wherever it is eligible.
-    // With an upsampled residual (FPN laterals) from 4 x igemm_ws_min pixels: p2's lateral 115 -> 107 us, p3's 39.7 -> 41.0 (tools/ws_ab.py)
-    if constexpr (sizeof(T) == 2)
-        if (!g_group && ws_ok(d) && (force == 14 || (force == 0 && tn.igemm_ws && (tn.igemm_direct & 1) && d.M >= (d.res_mode == 2 ? 4L : 1L) * tn.igemm_ws_min))) return launch_ws(d, st, tn.igemm_ws_wgs);
-    if (force == 5 || (force == 0 && d.Cout <= 16)) return launch<T, 128, 16, 4, 1, 4>(d, st);
-    if (force == 1) return launch<T, 128, 128, 2, 2, 4>(d, st);
-    if constexpr (sizeof(T) == 2) {
-        if (force == 2 && (direct & 1)) return d.res_mode ? launch<T, 128, 64, 4, 1, 4, true, false, 2>(d, st) : launch<T, 128, 64, 4, 1, 4, true, false, 1>(d, st);
-    }
-    if (force == 2) return launch<T, 128, 64, 4, 1, 4>(d, st);
-    if (force == 3) return launch<T, 64, 64, 2, 2, 4>(d, st);
-    if (force == 4) return launch<T, 256, 128, 4, 2, 4, false>(d, st);
-    if constexpr (sizeof(T) == 2) {
-        // 128-byte K slabs (64 channels: a full cache line per pixel row and k-step, half the barriers): plain 1x1 / linear
-        // layers only (a ragged K tail is handled for those).  igemm_k64_min: long-K layers (res4/res5 reductions, their dgrads,
-        // the box head's FCs) run 10-18 % faster on the 64x64 form than on any 32-channel tile (tools/igemm_sweep.py);
-        // short-K layers (4 slabs) lose more to the shallower pipeline than they gain.
-        const bool plain = d.KH * d.KW == 1 && d.stride == 1 && d.pad == 0;
-        if (plain && force == 6) return launch<T, 128, 128, 2, 2, 8, false>(d, st);
-        if (plain && force == 7) return launch<T, 128, 64, 4, 1, 8, false>(d, st);
-        if (plain && force == 12 && (direct & 1) && !d.res_mode && d.K % 64 == 0) return launch<T, 128, 64, 4, 1, 8, false, false, 1>(d, st);
-        const bool lin256 = tn.igemm_tile != 9 && big >= tn.igemm_lintile_min && d.K >= tn.igemm_bigtile_k;     // (the token-GEMM rule below wins)
-        if (plain && (force == 8 || (force == 0 && !lin256 && d.Cout > 64 && d.K % 64 == 0 && d.K >= tn.igemm_k64_min))) {
-            if ((direct & 2) && !d.res_mode) return launch<T, 64, 64, 2, 2, 8, false, false, 1>(d, st);
-            return launch<T, 64, 64, 2, 2, 8, false>(d, st);
-        }
-    }
-    // fp32 (the parity mode; the Deformable-DETR step's arithmetic): the f32-input MFMA runs at 1/16 of the bf16 rate, so a tile's K loop is
-    // long and what pays is workgroups, not bytes per flop -- 64 x 64 tiles are as fast or faster than every larger tile on all of that
-    // step's shapes (tools/f32_tile_sweep.py: 33 600 px x 128 -> 128 3x3 161 -> 110 us, 16 800 x 512 -> 128 77 -> 52, 44 646 x 256 -> 384
-    // 100 -> 85, 44 646 x 1024 -> 256 205 -> 201); same K order per output element as the other tap-form tiles (bit-identical results)
-    if (sizeof(T) == 4 && force == 0 && big < tn.igemm_f32_tile64_max) return launch<T, 64, 64, 2, 2, 4>(d, st);
-    if (d.Cout <= 64) return launch<T, 128, 64, 4, 1, 4>(d, st);
-    if (tn.igemm_tile != 9 && big >= tn.igemm_lintile_min && d.K >= tn.igemm_bigtile_k) {
-        // 128-byte K slabs on this tile for plain bf16 layers with K % 64 == 0 (+8-17 % on the box head's FC1 dgrad and the ViT linears,
-        // tools/lin_tile_ab.py; igemm_tile 7: the 64-byte slabs)
-        if constexpr (sizeof(T) == 2)
-            if (tn.igemm_tile != 7 && d.KH * d.KW == 1 && d.stride == 1 && d.pad == 0 && d.K % 64 == 0) return launch<T, 256, 128, 4, 2, 8, false>(d, st);
-        return launch<T, 256, 128, 4, 2, 4, false>(d, st);
-    }
-    if (big < 200) return launch<T, 64, 64, 2, 2, 4>(d, st);
-    // short-K layers (the bottlenecks' 1x1 expansions and res3's reductions: K = 128 .. 512, 4-16 slabs) are all prologue and
-    // epilogue: half-width tiles (twice the workgroups, half the staging epilogue each) run them 8-13 % faster than 128x128
-    // (tools/fc_dgrad_sweep.py: 16800 x 256 -> 1024: 25 -> 23 us, 67200 x 128 -> 512: 31 -> 27 us, 67200 x 512 -> 128: 26 -> 24 us)
-    if constexpr (sizeof(T) == 2) {
-        if (d.K <= tn.igemm_narrow_k && (direct & 1)) return d.res_mode ? launch<T, 128, 64, 4, 1, 4, true, false, 2>(d, st) : launch<T, 128, 64, 4, 1, 4, true, false, 1>(d, st);
-    }
-    if (sizeof(T) == 2 && d.K <= tn.igemm_narrow_k) return launch<T, 128, 64, 4, 1, 4>(d, st);
-    return launch<T, 128, 128, 2, 2, 4>(d, st);
+    return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: unknown tile");
 }
 
-}  // namespace
-
-namespace {
-int fill_convdev(const aldi_conv_args* a, ConvDev& d) {
-    if (!a || !a->x || !a->w || (!a->y && !a->y_f32)) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: null pointer");
-    const int bk = a->dtype == ALDI_BF16 ? 32 : 16;
-    const int ep = a->dtype == ALDI_BF16 ? 8 : 4;
-    if (a->dtype != ALDI_BF16 && a->dtype != ALDI_F32) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: bad dtype");
-    if (a->KH * a->KW == 1 ? (a->Cin % ep != 0) : (a->Cin % bk != 0))
-        return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: Cin must be a multiple of 32 (bf16) / 16 (f32) for KxK convs; of a 16-B chunk for 1x1");
-    if (a->Cout % 4 != 0) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: Cout must be a multiple of 4");
-    if (a->res_mode == 2 && ((a->Ho & 1) || (a->Wo & 1))) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: upsample residual needs even Ho,Wo");
-    if (a->res_mode && !a->res) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: res_mode set without res");
-    d.x = a->x; d.w = a->w; d.y = a->y; d.y_f32 = a->y_f32; d.scale = a->scale; d.shift = a->shift;
-    d.res = a->res; d.mask = a->mask;
-    d.N = a->N; d.H = a->H; d.W = a->W; d.Cin = a->Cin; d.Cout = a->Cout; d.KH = a->KH; d.KW = a->KW;
-    d.stride = a->stride; d.pad = a->pad; d.Ho = a->Ho; d.Wo = a->Wo;
-    d.relu = a->relu; d.res_mode = a->res_mode; d.out_scale = a->out_scale < 1 ? 1 : a->out_scale;
-    d.OH = a->OH; d.OW = a->OW;
-    long M = (long)a->N * a->Ho * a->Wo;
-    if (M <= 0 || M > 0x7fffffffL) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: bad M");
-    d.M = (int)M;
-    d.K = a->KH * a->KW * a->Cin;
-    const size_t esz = a->dtype == ALDI_BF16 ? 2 : 4;
-    const size_t xb = (size_t)a->N * a->H * a->W * a->Cin * esz, wb = (size_t)a->Cout * d.K * esz;
-    const size_t yb = (size_t)a->N * (d.out_scale > 1 ? (size_t)a->OH * a->OW : (size_t)a->Ho * a->Wo) * a->Cout * esz;
-    if (xb >= 0x80000000ull || wb >= 0x80000000ull || yb >= 0x80000000ull)
-        return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: operand larger than 2 GiB (32-bit buffer offsets)");
-    if (a->KH * a->KW > 16) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: at most 16 taps");
-    d.x_bytes = (unsigned)xb;
-    d.w_bytes = (unsigned)wb;
-    d.xcd = 0; d.dbg = 0;
-    d.ksplit = 0; d.slabs_per_split = 0; d.lean = 0;
-    d.mask_bits = static_cast<const unsigned char*>(a->mask_bits);
-    d.bits_out = static_cast<unsigned char*>(a->bits_out);
-    if ((a->mask_bits || a->bits_out) && (a->dtype != ALDI_BF16 || (a->Cout & 7) || d.out_scale != 1 || a->res_mode == 2 || !a->y || a->y_f32 || a->ksplit > 1))
-        return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: bit masks take bf16 outputs with Cout % 8 == 0 in the plain layout (no fp32 output, scatter, upsampled residual or split-K)");
-    if (a->mask_bits && a->mask) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: mask and mask_bits are alternatives");
-    return ALDI_OK;
-}
-}  // namespace
-
-namespace {
 // y[m][c] = act(scale[c] * sum_z ws[z][m][c] + shift[c]) -> bf16: the slices are added in slice order (deterministic)
 __global__ __launch_bounds__(256) void splitk_finalize_kernel(const float* __restrict__ ws, int ks, long mc, int C, const float* __restrict__ scale,
                                                               const float* __restrict__ shift, int relu, bf16_t* __restrict__ y) {
@@ -1422,79 +1183,59 @@ __global__ __launch_bounds__(256) void splitk_finalize_kernel(const float* __res
     *reinterpret_cast<uint2*>(y + e) = o;
 }
 
-int conv_splitk(const aldi_conv_args* a, ConvDev& d, hipStream_t st) {
-    const int ks = a->ksplit;
-    if (a->dtype != ALDI_BF16 || a->KH * a->KW != 1 || a->stride != 1 || a->pad != 0 || a->res_mode || a->mask || a->y_f32 || !a->y || !a->ws ||
-        (a->out_scale > 1) || d.K % (64 * ks) != 0 || ks > 64)
-        return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: split-K takes bf16 plain 1x1 / linear layers with K % (64 * ksplit) == 0, a workspace, no res / mask / fp32 output");
-    ConvDev s = d;
-    s.y = nullptr; s.y_f32 = static_cast<float*>(a->ws); s.scale = nullptr; s.shift = nullptr; s.relu = 0;
-    s.ksplit = ks;
-    s.xcd = aldi_tuning().igemm_xcd; s.dbg = aldi_tuning().igemm_dbg;
-    // igemm_splitk_tile: 0 = 128x128 tiles with 128-byte K slabs (4 waves); 1 = 256x128 tiles, 64-byte slabs (8 waves: two per SIMD
-    // also when the launch is one workgroup per CU: FC1 at 2048 rows 86 -> 72 us, at 2000 rows 94 -> 72 us, tools/fc1_splitk_sweep.py)
-    const int tile_knob = aldi_tuning().igemm_splitk_tile;       // 2 (default): 256x128 (128-byte slabs) when its launch still has ~one workgroup per CU; 4: the same rule with 64-byte slabs
-    const bool big_ok = (long)cdiv(d.M, 256) * cdiv(d.Cout, 128) * ks >= 200;
-    if (tile_knob == 3 || (tile_knob == 2 && big_ok)) {
-        // 256x128 tiles with 128-byte K slabs (full cache lines per DMA lane group, half the barriers per MFMA of the 64-byte form: FC1 at 2048
-        // rows 94 -> 79 us on cold weights, tools/fc1_cold.py)
-        s.slabs_per_split = d.K / 64 / ks;
-        if (int rc = launch<bf16_t, 256, 128, 4, 2, 8, false>(s, st)) return rc;
-    } else if (tile_knob == 1 || (tile_knob == 4 && big_ok)) {
-        s.slabs_per_split = d.K / 32 / ks;
-        if (int rc = launch<bf16_t, 256, 128, 4, 2, 4, false>(s, st)) return rc;
-    } else {
-        s.slabs_per_split = d.K / 64 / ks;
-        if (int rc = launch<bf16_t, 128, 128, 2, 2, 8, false>(s, st)) return rc;
+constexpr int kNameCap = 112;
+
+// One convolution: plan it (igemm_select.h), and unless `dry` enqueue it and note its name for aldi_last_dispatch().  name[kNameCap]: what ran / would run.
+int conv_one(const aldi_conv_args* a, const bool dry, hipStream_t st, char* name) {
+    ConvDev d;
+    Choice c;
+    if (int rc = plan_conv(a, aldi_tuning(), d, c)) return rc;
+    dispatch_name(c, name, kNameCap);
+    if (dry) return ALDI_OK;
+    if (int rc = launch_choice(c, d, nullptr, st)) return rc;
+    aldi_note_dispatch(name);
+    if (c.ksplit > 1) {             // d wrote the slices' fp32 partial tiles to a->ws
+        const long mc = (long)d.M * d.Cout;
+        hipLaunchKernelGGL(splitk_finalize_kernel, dim3(cdiv(mc / 4, 256)), dim3(256), 0, st, static_cast<const float*>(a->ws), c.ksplit, mc, d.Cout, a->scale, a->shift,
+                           a->relu, static_cast<bf16_t*>(a->y));
+        ALDI_CHECK_LAUNCH();
     }
-    const long mc = (long)d.M * d.Cout;
-    hipLaunchKernelGGL(splitk_finalize_kernel, dim3(cdiv(mc / 4, 256)), dim3(256), 0, st, static_cast<const float*>(a->ws), ks, mc, d.Cout, d.scale, d.shift,
-                       d.relu, static_cast<bf16_t*>(a->y));
-    ALDI_CHECK_LAUNCH();
+    return ALDI_OK;
+}
+
+// n convolutions: one launch when they are one layer shape, else n single ones (name: the last one's)
+int conv_many(const aldi_conv_args* args, const int n, const bool dry, hipStream_t st, char* name) {
+    if (!args || n < 1) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm_group: no problems");
+    if (n == 1 || !conv_group_same(args, n, aldi_tuning())) {
+        for (int i = 0; i < n; ++i)
+            if (int rc = conv_one(&args[i], dry, st, name)) return rc;
+        return ALDI_OK;
+    }
+    static thread_local ConvGroup G;
+    ConvDev d;
+    Choice c;
+    if (int rc = plan_conv_group(args, n, aldi_tuning(), G, d, c)) return rc;
+    dispatch_name(c, name, kNameCap);
+    if (dry) return ALDI_OK;
+    if (int rc = launch_choice(c, d, &G, st)) return rc;
+    aldi_note_dispatch(name);
     return ALDI_OK;
 }
 }  // namespace
 
 extern "C" int aldi_conv_igemm(const aldi_conv_args* a, aldi_stream_t stream) {
-    ConvDev d;
-    if (int rc = fill_convdev(a, d)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (a->ksplit > 1) return conv_splitk(a, d, st);
-    if (a->dtype == ALDI_BF16) return dispatch<bf16_t>(d, st);
-    return dispatch<float>(d, st);
+    char name[kNameCap];
+    return conv_one(a, false, static_cast<hipStream_t>(stream), name);
 }
 
 extern "C" int aldi_conv_igemm_group(const aldi_conv_args* args, int n, aldi_stream_t stream) {
-    if (!args || n < 1) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm_group: no problems");
-    bool same = n <= kMaxConvGroup && aldi_tuning().igemm_group;
-    for (int i = 1; i < n && same; ++i) {
-        const aldi_conv_args &a = args[0], &b = args[i];
-        // one layer shape: everything that selects code paths inside the kernel template is equal; N, H x W (pyramid levels) and the
-        // tensors differ -- the tile heuristics look at the pixel count, Cout, K and the conv geometry ("same" padding or not) only
-        same = a.dtype == b.dtype && a.Cin == b.Cin && a.Cout == b.Cout && a.KH == b.KH && a.KW == b.KW &&
-               a.stride == b.stride && a.pad == b.pad && (a.Ho == a.H) == (b.Ho == b.H) && (a.Wo == a.W) == (b.Wo == b.W) && a.out_scale == b.out_scale &&
-               (a.y != nullptr) == (b.y != nullptr) && (a.y_f32 != nullptr) == (b.y_f32 != nullptr);
-    }
-    if (!same || n == 1) {
-        for (int i = 0; i < n; ++i)
-            if (int rc = aldi_conv_igemm(&args[i], stream)) return rc;
-        return ALDI_OK;
-    }
-    static thread_local ConvGroup G;
-    G.n = n;
-    long Msum = 0;
-    for (int i = 0; i < n; ++i) {
-        if (int rc = fill_convdev(&args[i], G.p[i])) return rc;
-        Msum += G.p[i].M;
-    }
-    for (int i = 1; i < n; ++i)         // largest problem first: the small ones' tiles fill its tail
-        for (int j = i; j > 0 && G.p[j].M > G.p[j - 1].M; --j) { const ConvDev t_ = G.p[j]; G.p[j] = G.p[j - 1]; G.p[j - 1] = t_; }
-    // the tile template is chosen for the COMBINED pixel count (the heuristics look at M, Cout, K and the conv geometry only)
-    ConvDev d = G.p[0];
-    d.M = (int)(Msum > 0x7fffffffL ? 0x7fffffffL : Msum);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    g_group = &G;
-    const int rc = args[0].dtype == ALDI_BF16 ? dispatch<bf16_t>(d, st) : dispatch<float>(d, st);
-    g_group = nullptr;
+    char name[kNameCap];
+    return conv_many(args, n, false, static_cast<hipStream_t>(stream), name);
+}
+
+extern "C" int aldi_conv_igemm_plan(const aldi_conv_args* args, int n, char* name, int cap) {
+    char buf[kNameCap] = "";
+    const int rc = n == 1 ? conv_one(args, true, nullptr, buf) : conv_many(args, n, true, nullptr, buf);
+    if (rc == ALDI_OK && name && cap > 0) snprintf(name, (size_t)cap, "%s", buf);
     return rc;
 }

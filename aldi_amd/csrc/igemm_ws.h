@@ -237,30 +237,17 @@ __global__ __launch_bounds__(256, 2) void igemm_ws_kernel(ConvDev p, const int n
     }
 }
 
-// eligible: bf16, 1x1 / stride 1 / no padding, plain output layout, K = Cin in {64, 128, 256, 512}, whole channel groups, no full-tensor mask / fp32
-// output / split-K
-inline int ws_channels(int K) { return K == 64 || K == 128 ? 256 : K == 256 || K == 512 ? 128 : 0; }      // BN of the instantiation for this K
-inline bool ws_ok(const ConvDev& d) {
-    const int bn = ws_channels(d.K);
-    return d.KH * d.KW == 1 && d.stride == 1 && d.pad == 0 && d.K == d.Cin && bn && d.Cout % bn == 0 && d.y && !d.y_f32 && !d.mask && d.out_scale == 1 &&
-           d.ksplit <= 1 && (long)d.M * d.Cout * 2 < (1L << 31);
-}
-int launch_ws(const ConvDev& d, hipStream_t st, int wgs) {
-    const int bn = ws_channels(d.K), ncg = d.Cout / bn;
-    const int bm = d.K <= 256 ? 32 : 16;
-    const int n_mtiles = cdiv(d.M, bm);
+// (which layers it takes: ws_ok, igemm_select.h)  BM x BN per step over K = 8 * KC channels: a WS row of IGEMM_TILES
+template <typename T, int BM, int BN, int WM, int WN, int KC, bool PIPE, int EPI>
+int launch_WS(const Choice& c, const ConvDev& d, const ConvGroup*, hipStream_t st) {
+    const int ncg = d.Cout / BN;
+    const int n_mtiles = cdiv(d.M, BM);
     // whole sets of 8 x ncg workgroups (one per XCD and channel group); no more pixel-tile sequences than pixel tiles
-    int sets = wgs / (8 * ncg);
+    int sets = c.ws_wgs / (8 * ncg);
     if (sets < 1) sets = 1;
     if (sets > cdiv(n_mtiles, 8)) sets = cdiv(n_mtiles, 8);
     const dim3 grid(sets * 8 * ncg), block(256);
-    if (d.K == 64) hipLaunchKernelGGL((igemm_ws_kernel<2, 2, 4>), grid, block, 0, st, d, n_mtiles, ncg);
-    else if (d.K == 128) hipLaunchKernelGGL((igemm_ws_kernel<4, 2, 4>), grid, block, 0, st, d, n_mtiles, ncg);
-    else if (d.K == 256) hipLaunchKernelGGL((igemm_ws_kernel<8, 2, 2>), grid, block, 0, st, d, n_mtiles, ncg);
-    else hipLaunchKernelGGL((igemm_ws_kernel<16, 1, 2>), grid, block, 0, st, d, n_mtiles, ncg);
+    hipLaunchKernelGGL((igemm_ws_kernel<KC / 4, BM / 16, BN / 64>), grid, block, 0, st, d, n_mtiles, ncg);
     ALDI_CHECK_LAUNCH();
-    char name[112];
-    snprintf(name, sizeof(name), "igemm_ws<bf16,%d,%d,k%d>", bm, bn, d.K);
-    aldi_note_dispatch(name);
     return ALDI_OK;
 }

@@ -58,7 +58,9 @@ int aldi_noop(aldi_stream_t stream);
  *   igemm_halo_ilv       1 = the 256x256 halo64 tile runs its interleaved K loop (reads / DMA pieces between the MFMAs; 0 = the lockstep loop of r05)
  *   igemm_ws             1 = plain 1x1 bf16 layers with K = Cin in {64, 128, 256, 512}, whole groups of 256 (K >= 256: 128) output channels and at least
  *                        igemm_ws_min (40000: res3 / p2-size maps of the student; measured equal or slower below) pixels run the weight-stationary persistent kernel (igemm_ws.h: weights in registers, pixel tiles streamed
- *                        through a 3-stage LDS ring, epilogue from the accumulators); igemm_ws_wgs (512) = its workgroup count; igemm_force 14 forces it
+ *                        through a 3-stage LDS ring, epilogue from the accumulators); igemm_force 14 forces it
+ *   igemm_ws_min         least pixel count of a layer for igemm_ws (40000; with an upsampled residual: four times this)
+ *   igemm_ws_wgs         workgroup count of the weight-stationary kernel (512)
  *   igemm_lean           1 = plain 1x1 / linear layers with K % 64 == 0 on those tiles run the lean K loop (running DMA offsets)
  *   igemm_halo           1 = 3x3/stride-1/pad-1 bf16 convs use the halo form (one pixel slab per three taps)
  *   igemm_bigtile_min    128x128-tile count from which a 3x3 conv takes the big halo tile (1024)
@@ -85,6 +87,7 @@ int aldi_noop(aldi_stream_t stream);
  *   wgrad_big_group      1 = a group's layers with Cout % 256 == K % 256 == 0 run as ONE launch of 256x256 tiles (default)
  *   wgrad_big_epi        cost of one 256x256 epilogue in the group's split model, in 32-pixel slab steps (12)
  *   wgrad_big_group_min  (256x256 tiles x pixels) / 4096 a group needs for that launch (64); less: its layers join the 128x128 group
+ *   wgrad_lds_pad_kb     KB of unused dynamic LDS added to the grouped lean weight-gradient launch (0; caps its workgroups per CU: an occupancy experiment)
  *   wgrad_db             1 = grouped weight gradients with two LDS images and one barrier per 64-pixel slab (64 KB, two workgroups per CU)
  *   roialign_sep         1 = aldi_roialign forward in the separable form (row / column weight tables, one workgroup per ROI); 0 = per sample
  *   roialign_bwd_rows    2 = aldi_roialign_backward on bf16 pooled gradients with two feature rows per workgroup; 1 = one row (same results)
@@ -154,6 +157,11 @@ int aldi_conv_igemm(const aldi_conv_args* a, aldi_stream_t stream);
  * applied to several pyramid levels (FPN output convs, the RPN conv on p2..p6) -- in ONE launch; any other combination (or
  * igemm_group = 0) falls back to n single launches.  Same arithmetic as n aldi_conv_igemm calls. */
 int aldi_conv_igemm_group(const aldi_conv_args* args, int n, aldi_stream_t stream);
+/* Dry run: which kernel aldi_conv_igemm (n == 1) or aldi_conv_igemm_group (n > 1) would run for these arguments under the current tuning
+ * knobs.  Same argument checks, same status and error text; writes the name aldi_last_dispatch() would report afterwards (for a group that
+ * falls back to single launches: the last one's) to name[cap].  Launches nothing, needs no GPU, leaves aldi_last_dispatch() alone, and
+ * never dereferences the tensor pointers: only which of them are null matters. */
+int aldi_conv_igemm_plan(const aldi_conv_args* args, int n, char* name, int cap);
 
 /* Weight gradient: dw[Cout][KH][KW][Cin] (fp32) += scale[co] * sum_pixels g[p][co] * x[pix(p,kh,kw)][ci].
  * Accumulates into dw (split-K over pixels -- ordered through `ws`, or float atomics without it -- and over micro-steps); zero dw once

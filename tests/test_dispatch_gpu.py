@@ -90,6 +90,22 @@ def _mk(N, H, W_, Cin, Cout, k, seed, dtype):
     return x, w, g
 
 
+def _planned(x, w, **kw):
+    """what aldi_conv_igemm_plan names for this ops.conv2d call under the current knobs (nothing is launched).  ops._conv_args allocates the
+    output it points at and knows no split-K: the callers' shapes have K < 4096 or a residual, where ops.conv2d chooses none either (a
+    disagreement would show as a ' splitk' suffix on one side only)"""
+    from aldi_amd import _lib as L
+    from aldi_amd import ops
+    return L.plan_dispatch(ops._conv_args(x, w, **kw)[0])
+
+
+def _planned_group(calls):
+    from aldi_amd import _lib as L
+    from aldi_amd import ops
+    arr = (L.ConvArgs * len(calls))(*[ops._conv_args(x, w, **kw)[0] for x, w, kw in calls])
+    return L.plan_dispatch(arr, len(calls))
+
+
 def _check_forward(case, dtype, expect, *, force=None, full=True):
     from aldi_amd import _lib as L
     from aldi_amd import ops
@@ -106,8 +122,11 @@ def _check_forward(case, dtype, expect, *, force=None, full=True):
     L.set_tuning("igemm_direct", 0)          # these cases are about the tile templates with the STAGED epilogue (the direct one: _check_direct below)
     if force is not None:
         L.set_tuning("igemm_force", force)
-    y = ops.conv2d(xd, wd, stride=stride, pad=pad, scale=scale.to(dev), shift=shift.to(dev), res=rd, res_mode=1, relu=True)
+    kw = dict(stride=stride, pad=pad, scale=scale.to(dev), shift=shift.to(dev), res=rd, res_mode=1, relu=True)
+    planned = _planned(xd, wd, **kw)
+    y = ops.conv2d(xd, wd, **kw)
     name = L.last_dispatch()
+    assert planned == name, (planned, name)
     y32 = ops.conv2d(xd, wd, stride=stride, pad=pad, want_f32=True)          # plain epilogue, fp32 side output
     torch.cuda.synchronize()
     assert name == expect, (name, expect)
@@ -633,9 +652,11 @@ def test_conv_group_equals_single_launches(geo, batches, expect):
         calls.append((x, w, kw))
         singles.append(ops.conv2d(x, w, **kw))
     single_name = L.last_dispatch()
+    planned = _planned_group(calls)
     outs = ops.conv2d_group(calls)
     name = L.last_dispatch()
     torch.cuda.synchronize()
+    assert planned == name, (planned, name)
     assert name == expect, (name, single_name)
     for (x, w, kw), a, b in zip(calls, outs, singles):
         assert a.shape == b.shape
@@ -709,10 +730,39 @@ def test_conv_group_of_different_layers_falls_back():
     x2 = torch.randn(2, 10, 12, 32, device="cuda").bfloat16()
     w1 = torch.randn(64, 3, 3, 64, device="cuda").bfloat16()
     w2 = torch.randn(64, 3, 3, 32, device="cuda").bfloat16()
+    planned = _planned_group([(x1, w1, dict(pad=1)), (x2, w2, dict(pad=1))])
     a, b = ops.conv2d_group([(x1, w1, dict(pad=1)), (x2, w2, dict(pad=1))])          # different Cin: not one layer shape
     assert not L.last_dispatch().startswith("igemm_group")
+    assert planned == L.last_dispatch(), (planned, L.last_dispatch())
     torch.cuda.synchronize()
     assert torch.equal(a, ops.conv2d(x1, w1, pad=1)) and torch.equal(b, ops.conv2d(x2, w2, pad=1))
+
+
+def test_plan_names_a_fallen_back_group_and_a_splitk_linear():
+    """aldi_conv_igemm_plan before the call == aldi_last_dispatch() after it, where the call is more than one launch: a group of two different
+    layers (single launches: the last one's name) and a split-K linear (the slices' kernel; the finalize pass has no name)"""
+    from aldi_amd import _lib as L
+    from aldi_amd import ops
+    calls = []
+    for (N, H, W_, Cin, Cout, k, stride, pad) in (SMALL[0], SMALL[3]):
+        x, w, _ = _mk(N, H, W_, Cin, Cout, k, 3, torch.bfloat16)
+        calls.append((x.to("cuda", torch.bfloat16), w.to("cuda", torch.bfloat16), dict(stride=stride, pad=pad)))
+    planned = _planned_group(calls)
+    outs = ops.conv2d_group(calls)
+    assert planned == L.last_dispatch() == "igemm<bf16,64,64,2,2,pipe,tap>", (planned, L.last_dispatch())
+    for (x, w, kw), y in zip(calls, outs):
+        assert torch.equal(y, ops.conv2d(x, w, **kw))
+    x, w, _ = _mk(130, 1, 1, 4096, 136, 1, 4, torch.bfloat16)
+    x, w = x.to("cuda", torch.bfloat16), w.to("cuda", torch.bfloat16)
+    a, _ = ops._conv_args(x, w)
+    ws = torch.empty(4 * 130 * 136, dtype=torch.float32, device="cuda")
+    a.ws, a.ksplit = ws.data_ptr(), 4
+    planned = L.plan_dispatch(a)
+    y = ops.conv2d(x, w, ksplit=4)
+    assert planned == L.last_dispatch() == "igemm<bf16,128,128,2,2,flat,tap,k64> splitk", (planned, L.last_dispatch())
+    ref = ops.conv2d(x, w, ksplit=0, want_f32=True)
+    torch.cuda.synchronize()
+    assert (y.float() - ref).abs().max().item() <= 2.0 ** -7 * max(1.0, ref.abs().max().item())
 
 
 @pytest.mark.parametrize("k,pad", [(3, 1), (1, 0)])
@@ -730,9 +780,11 @@ def test_conv_group_over_pyramid_levels(k, pad):
         w = (torch.randn(256, k, k, 256, generator=gen) * 0.05).to("cuda", torch.bfloat16)
         sh = torch.randn(256, generator=gen).to("cuda")
         calls.append((x, w, dict(pad=pad, shift=sh, relu=True)))
+    planned = _planned_group(calls)
     outs = ops.conv2d_group(calls)
     name = L.last_dispatch()
     torch.cuda.synchronize()
+    assert planned == name, (planned, name)
     assert name.startswith("igemm_group9<"), name
     assert ("halo64" in name) == (k == 3), name
     for (x, w, kw), y in zip(calls, outs):
@@ -898,9 +950,11 @@ def _check_direct(case, kind, expect, *, force=None):
         kw.update(mask_bits=mb)
     if force is not None:
         L.set_tuning("igemm_force", force)
+    planned = _planned(xd, wd, **kw)
     y = ops.conv2d(xd, wd, **kw)
     name = L.last_dispatch()
     torch.cuda.synchronize()
+    assert planned == name, (planned, name)
     assert name == expect, (name, expect)
     pix = _sample_pixels(N, Ho, Wo)
     ref = _conv_ref_at(x, w, pix, stride, pad, Ho, Wo)
@@ -1130,10 +1184,14 @@ def test_halo64_group_over_pyramid_levels():
     calls = []
     for (N, H, W_) in ((2, 200, 336), (2, 100, 168), (2, 50, 84), (2, 25, 42), (2, 13, 21)):
         calls.append((torch.randn(N, H, W_, 256, generator=gen).to(dev, torch.bfloat16), w, dict(pad=1, shift=sh, relu=True)))
+    planned = _planned_group(calls)
     outs = ops.conv2d_group(calls)
+    assert planned == L.last_dispatch(), (planned, L.last_dispatch())
     assert L.last_dispatch() == "igemm_group5<bf16,256,256,4,2,halo64,direct>", L.last_dispatch()
     L.set_tuning("igemm_bigtile", 4)
+    planned = _planned_group(calls)
     refs = ops.conv2d_group(calls)
+    assert planned == L.last_dispatch(), (planned, L.last_dispatch())
     assert L.last_dispatch() == "igemm_group5<bf16,256,128,4,2,flat,halo>", L.last_dispatch()
     torch.cuda.synchronize()
     for a, b in zip(outs, refs):
