@@ -100,6 +100,15 @@ def plan_dispatch(args, n: int = 1) -> str:
     return buf.value.decode()
 
 
+def plan_wgrad_dispatch(args, n: int = 1, group: bool = False):
+    """aldi_conv_wgrad_plan: -> (name, workspace bytes) of aldi_conv_wgrad (args a WgradArgs or an array; group False) / aldi_conv_wgrad_group
+    (an array of n; group True) under the current knobs -- nothing is launched, no GPU is needed and no pointer is dereferenced"""
+    buf = C.create_string_buffer(224)
+    ws = C.c_long(0)
+    call("aldi_conv_wgrad_plan", C.byref(args) if isinstance(args, C.Structure) else args, n, int(group), buf, len(buf), C.byref(ws))
+    return buf.value.decode(), ws.value
+
+
 class BoxLossChunk(C.Structure):
     """aldi_box_loss_chunk (include/aldi_hip.h)"""
     _fields_ = [("r0", c_int), ("r1", c_int), ("grad_scale_cls", c_float), ("grad_scale_box", c_float), ("loss_box", c_void_p),

@@ -16,24 +16,17 @@
 //
 // Replaces cuDNN/MIOpen wgrad + torch Linear weight grad reached through autograd from
 // aldi/trainer.py:79 (`trainer.do_backward`).
+//
+// This file holds the kernels and ONE executor.  Which kernels a call launches, with what pixel splits and which workspace -- the plan --
+// is host-only code in wgrad_select.h (the kernels' argument structs WgDev / WgGroup / WgFin live there too); the entry points at the
+// bottom are "plan, check that the workspace fits, execute": every launch of the plan, then the ordered epilogue's finalize pass.
 #include "common.h"
+#include "wgrad_select.h"
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 namespace {
-
-struct WgDev {
-    const void* x; const void* g; float* dw; const float* scale; float* db;
-    int N, H, W, Cin, Cout, KH, KW, stride, pad, Ho, Wo;
-    int M, K, pix_per_split, ident, xcd, dbg;
-    unsigned x_bytes, g_bytes, dw_bytes;
-    // ordered epilogue (no float atomics): a pixel split writes its partial tile to `ws` (fragment order, 16 B per lane) and its
-    // partial bias sums to `wsb`; wgrad_finalize_kernel adds the splits IN ORDER to dw / db.  splits == 1: the only owner of a tile
-    // adds to dw with plain loads and stores.  ordered == 0: the float-atomic epilogue (callers without a workspace).
-    float* ws; float* wsb;
-    int splits, ordered;
-};
 
 __device__ __forceinline__ int swz8(int row, int c) { return c ^ ((row >> 1) & 7); }
 
@@ -442,18 +435,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void w
     __shared__ uint4 lds[2 * 128 * 8];
     wgrad_bf16_lean_body<128, 128, 2, 2>(p, lds);
 }
-// Grouped form: the weight gradients of SEVERAL layers in one launch.  A bottleneck stage's layers are small GEMMs (16-36 output
-// tiles each) over the same 16800 pixels; launched one by one each needs an 11-24-way pixel split to occupy the chip, and every
-// split ends in 16 K float atomics -- 20-50 % of the kernel time (tools/wgrad_sweep.py) -- plus a launch and a tail per layer.
-// The backward pass does not need them one by one (nothing reads a weight gradient before the optimizer), so the engine
-// collects a stage's layers and launches them together: hundreds of tiles, (almost) no pixel split, a handful of atomics.
-constexpr int kMaxGroup = 24;
-struct WgGroup {
-    int n;
-    int wg_begin[kMaxGroup + 1];      // first workgroup of each problem; wg_begin[n] = grid size
-    int gx[kMaxGroup], gy[kMaxGroup], gz[kMaxGroup]; // output tiles and pixel splits of each problem (its workgroups: tile-fastest, then split)
-    WgDev p[kMaxGroup];
-};
+// Grouped form: the weight gradients of SEVERAL layers in one launch (WgGroup, wgrad_select.h).
 // Which (problem, tile, pixel split) does workgroup `bid` of a grouped launch work on.  XCD-aware order over the WHOLE group: workgroup b
 // runs on XCD b % 8 (observed dispatch); every XCD gets one contiguous range of the group's (problem, split, tile) list, tile fastest,
 // so the workgroups resident in an XCD at the same time are neighbours in that list -- the tiles of one pixel range, which re-read the
@@ -508,17 +490,7 @@ __global__ __launch_bounds__(512) void wgrad_bf16_big_group_kernel(WgGroup G) {
     wgrad_bf16_lean_tile<256, 256, 2, 4>(G.p[i], lds, tx, ty, bz);
 }
 
-// Second pass of the ordered epilogue: dw += scale * (split 0 + split 1 + ...), db += (...), the splits in index order -- the
-// same bits on every run, and plain loads / stores.  One 256-thread workgroup per (tile, fragment, 4 waves of the producer).
-struct WgFinItem {
-    const float* ws; const float* wsb; float* dw; float* db; const float* scale;
-    int Cout, K, gx, gy, S, big;
-};
-struct WgFin {
-    int n;
-    int wg_begin[kMaxGroup + 1];
-    WgFinItem it[kMaxGroup];
-};
+// Second pass of the ordered epilogue (WgFin, wgrad_select.h): the splits of every tile added in index order.
 template <int TCO, int TKK, int WM, int WN>
 __device__ __forceinline__ void wgrad_finalize_part(const WgFinItem& it, int local) {
     constexpr int TM = TCO / WM / 16, TN = TKK / WN / 16, NW = WM * WN, NF = TM * TN, HALVES = NW / 4;
@@ -1260,329 +1232,86 @@ __global__ __launch_bounds__(NT) void colsum_kernel(const T* __restrict__ g, flo
     }
 }
 
-}  // namespace
-
-namespace {
-// validated device-side description of one weight-gradient problem
-int fill_wgdev(const aldi_wgrad_args* a, WgDev& d) {
-    if (!a || !a->x || !a->g || !a->dw) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad: null pointer");
-    const int ep = a->dtype == ALDI_BF16 ? 8 : 4;
-    if (a->Cin % ep || a->Cout % ep) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad: Cin/Cout must be multiples of a 16-B chunk");
-    d.x = a->x; d.g = a->g; d.dw = a->dw; d.scale = a->scale; d.db = a->db;
-    d.N = a->N; d.H = a->H; d.W = a->W; d.Cin = a->Cin; d.Cout = a->Cout; d.KH = a->KH; d.KW = a->KW;
-    d.stride = a->stride; d.pad = a->pad; d.Ho = a->Ho; d.Wo = a->Wo;
-    long M = (long)a->N * a->Ho * a->Wo;
-    if (M <= 0 || M > 0x7fffffffL) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad: bad M");
-    d.M = (int)M;
-    d.K = a->KH * a->KW * a->Cin;
-    const size_t esz = a->dtype == ALDI_BF16 ? 2 : 4;
-    const size_t xb = (size_t)a->N * a->H * a->W * a->Cin * esz, gb = (size_t)M * a->Cout * esz;
-    if (a->dtype == ALDI_BF16 && (xb >= 0x80000000ull || gb >= 0x80000000ull))
-        return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad: operand larger than 2 GiB (32-bit buffer offsets)");
-    d.x_bytes = (unsigned)xb;
-    d.g_bytes = (unsigned)gb;
-    const size_t wb = (size_t)a->Cout * d.K * 4;
-    if (wb >= 0x80000000ull) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad: gradient larger than 2 GiB (32-bit buffer offsets)");
-    d.dw_bytes = (unsigned)wb;
-    d.ident = (a->KH == 1 && a->KW == 1 && a->stride == 1 && a->pad == 0 && a->Ho == a->H && a->Wo == a->W) ? 1 : 0;
-    d.pix_per_split = d.M; d.xcd = 0; d.dbg = 0;
-    d.ws = d.wsb = nullptr; d.splits = 1; d.ordered = 0;
-    return ALDI_OK;
-}
-bool lean_eligible(const aldi_wgrad_args* a, const WgDev& d) {
-    const bool same = a->stride == 1 && a->Ho == a->H && a->Wo == a->W && 2 * a->pad == a->KH - 1 && a->KH == a->KW && a->Cin % 64 == 0;
-    return a->dtype == ALDI_BF16 && (d.ident || same);
-}
-// 256x256 tile (one 8-wave workgroup per CU) when every workgroup still gets a long pixel range
-bool wants_big_tile(const WgDev& d, const AldiTuning& tn) {
-    if (tn.wgrad_big_min <= 0 || d.Cout % 256 || d.K % 256) return false;
-    const int tb = (d.Cout / 256) * (d.K / 256);
-    const int sb = tn.wgrad_big_slots / tb;            // floor: one 8-wave workgroup per CU, never 257 of them
-    return cdiv(d.M, 64) / (sb > 0 ? sb : 1) >= tn.wgrad_big_min;
-}
-}  // namespace
-
-namespace {
-// Workspace of the ordered epilogue, carved in 256-B units.  dry: count only (aldi_conv_wgrad_group_workspace).
-struct WsCarver {
-    float* base; size_t cap, used; bool dry;
-    float* take(size_t n_floats) {
-        n_floats = (n_floats + 63) / 64 * 64;
-        float* r = dry ? nullptr : base + used;
-        used += n_floats;
-        return r;
-    }
-    bool fits() const { return dry || used <= cap; }
-};
-// the problems of one call that need the second pass; flushed in batches of kMaxGroup
-struct FinBuilder {
-    WgFin F; int wg; bool dry; hipStream_t st;
-    FinBuilder(hipStream_t s, bool d) : wg(0), dry(d), st(s) { F.n = 0; }
-    void add(const WgDev& d, int big) {
-        if (dry) return;
-        if (F.n == kMaxGroup) flush();
-        const int tile = big ? 256 : 128, gx = cdiv(d.Cout, tile), gy = cdiv(d.K, tile);
-        WgFinItem& it = F.it[F.n];
-        it.ws = d.ws; it.wsb = d.wsb; it.dw = d.dw; it.db = d.db; it.scale = d.scale;
-        it.Cout = d.Cout; it.K = d.K; it.gx = gx; it.gy = gy; it.S = d.splits; it.big = big;
-        F.wg_begin[F.n] = wg;
-        wg += gx * gy * (big ? 32 * 2 : 16) + 1;           // (tile, fragment, four producer waves) + the bias workgroup
-        ++F.n;
-    }
-    void flush() {
-        if (dry || F.n == 0) return;
-        for (int k = F.n; k <= kMaxGroup; ++k) F.wg_begin[k] = wg;
-        hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(wg), dim3(256), 0, st, F);
-        F.n = 0; wg = 0;
-    }
-};
-// ordered epilogue of problem d (tile x tile output tiles, d.splits pixel ranges): workspace + second pass when split
-void plan_ordered(WgDev& d, int big, WsCarver& ws, FinBuilder& fin) {
-    d.ordered = 1;
-    d.ws = d.wsb = nullptr;
-    if (d.splits <= 1) return;
-    const int tile = big ? 256 : 128;
-    const size_t gx = cdiv(d.Cout, tile), gy = cdiv(d.K, tile);
-    d.ws = ws.take(gx * gy * (size_t)d.splits * tile * tile);
-    if (d.db) d.wsb = ws.take(gx * (size_t)d.splits * tile);
-    fin.add(d, big);
+// the plan of the call in flight (thread-local storage: cleared, not freed, between calls)
+WgPlan& plan_storage() {
+    static thread_local WgPlan P;
+    return P;
 }
 
-int wgrad_single(const aldi_wgrad_args* a, hipStream_t st, WsCarver& ws, FinBuilder& fin, bool ordered, bool dry) {
-    WgDev d;
-    if (int rc = fill_wgdev(a, d)) return rc;
-    const AldiTuning& tn = aldi_tuning();
-    const int lean_env = tn.wgrad_lean, big_slots_env = tn.wgrad_big_slots;
-    const bool same = a->stride == 1 && a->Ho == a->H && a->Wo == a->W && 2 * a->pad == a->KH - 1 && a->KH == a->KW && a->Cin % 64 == 0;
-    const bool lean = a->dtype == ALDI_BF16 && lean_env && (d.ident || same);
-    const bool big = lean && wants_big_tile(d, tn);
-    const bool f32_t128 = a->dtype == ALDI_F32 && tn.wgrad_f32_tile128 && d.Cout >= 128 && d.K >= 128;
-    const int tile = big ? 256 : (a->dtype == ALDI_BF16 || f32_t128 ? 128 : 64);
-    const int bp = a->dtype == ALDI_BF16 ? 64 : (f32_t128 ? 32 : 16);
-    int slabs = cdiv(d.M, bp);
-    int tiles = cdiv(d.Cout, tile) * cdiv(d.K, tile);
-    const int slots_env_ = tn.wgrad_slots;
-    const int slots_env = big ? big_slots_env : (f32_t128 ? 512 : slots_env_);      // fp32 128x128: two workgroups per CU (VGPRs), MFMA-bound: whole rounds
-    // the kernel is bound per CU (L2 -> CU path, LDS), not by latency: few, long splits (1-2 workgroups per CU) beat
-    // many short ones, whose epilogues also contend on the same dW lines
-    int splits = big ? slots_env / tiles : cdiv(slots_env, tiles);
-    if (f32_t128) {
-        // MFMA-bound, two workgroups per CU: the launch runs in rounds of 512 workgroups, a round lasting (slabs per split + an
-        // epilogue of ~6 slabs: 16 K float atomics per workgroup).  cdiv(512, tiles) splits put 576 workgroups = two rounds on
-        // res5's 3x3 (169 us against 150 for the 64x64 kernel)
-        long best = -1;
-        int best_sp = 1;
-        for (int sp = 1; sp <= 512 && sp <= (slabs + 3) / 4; ++sp) {
-            const long rounds = ((long)tiles * sp + 511) / 512;
-            const long cost = rounds * (cdiv(slabs, sp) + 6);
-            if (best < 0 || cost < best) { best = cost; best_sp = sp; }
+// every launch of the plan, the bias passes where it says so, THEN the finalize launches in batches of kMaxGroup, then the dispatch note
+int execute_plan(const WgPlan& P, hipStream_t st) {
+    for (const WgLaunch& L : P.launches) {
+        const dim3 grid(L.gx, L.gy, L.gz), block(kWgForms[L.form].threads);
+        const WgDev& d = L.d;
+        const WgGroup& G = P.groups[L.group];
+        switch (L.form) {
+        case WG_GENERIC: hipLaunchKernelGGL(wgrad_bf16_kernel, grid, block, 0, st, d); break;
+        case WG_LEAN: hipLaunchKernelGGL(wgrad_bf16_lean_kernel, grid, block, 0, st, d); break;
+        case WG_BIG: hipLaunchKernelGGL(wgrad_bf16_big_kernel, grid, block, 0, st, d); break;
+        case WG_BIG64:
+            if (L.ilv) hipLaunchKernelGGL(wgrad_bf16_big64_kernel<true>, grid, block, 0, st, d);
+            else hipLaunchKernelGGL(wgrad_bf16_big64_kernel<false>, grid, block, 0, st, d);
+            break;
+        case WG_DMA: hipLaunchKernelGGL((wgrad_bf16_dma_kernel<128, 128, 2, 2>), grid, block, 0, st, d); break;
+        case WG_F32: hipLaunchKernelGGL(wgrad_f32_kernel, grid, block, 0, st, d); break;
+        case WG_F32_T128: hipLaunchKernelGGL(wgrad_f32_t128_kernel<32>, grid, block, 0, st, d); break;
+        case WG_LEAN_GROUP: hipLaunchKernelGGL(wgrad_bf16_lean_group_kernel, grid, block, (size_t)L.lds, st, G); break;
+        case WG_LEAN_GROUP_DB: hipLaunchKernelGGL(wgrad_bf16_lean_group_db_kernel, grid, block, 0, st, G); break;
+        case WG_LEAN64_GROUP:
+            if (L.ilv) hipLaunchKernelGGL(wgrad_bf16_lean64_group_kernel<true>, grid, block, 0, st, G);
+            else hipLaunchKernelGGL(wgrad_bf16_lean64_group_kernel<false>, grid, block, 0, st, G);
+            break;
+        case WG_BIG_GROUP: hipLaunchKernelGGL(wgrad_bf16_big_group_kernel, grid, block, 0, st, G); break;
+        case WG_BIG64_GROUP:
+            if (L.ilv) hipLaunchKernelGGL(wgrad_bf16_big64_group_kernel<true>, grid, block, 0, st, G);
+            else hipLaunchKernelGGL(wgrad_bf16_big64_group_kernel<false>, grid, block, 0, st, G);
+            break;
+        default: return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad: bad launch form");
         }
-        splits = best_sp;
-    }
-    if (splits > slabs / 4) splits = slabs / 4;    // ... but at least 4 slabs of work behind every epilogue
-    if (splits < 1) splits = 1;
-    if (splits > 512) splits = 512;
-    int slabs_per = cdiv(slabs, splits);
-    d.pix_per_split = slabs_per * bp;
-    splits = cdiv(d.M, d.pix_per_split);
-    dim3 grid(cdiv(d.Cout, tile), cdiv(d.K, tile), splits);
-    d.xcd = tn.wgrad_xcd;
-    d.dbg = tn.wgrad_dbg;
-    d.splits = splits;
-    const char* which;
-    // LDS-DMA + transpose-read form (wgrad_dma: 0 off, 1 = 128x128 tile in place of the lean kernel, 2 = also in place of the 256x256 one)
-    const bool dma = lean && tn.wgrad_dma > 0 && (d.ident ? a->Cin % 8 == 0 : a->Cin % 16 == 0) && a->KH * a->KW <= 25 && !(big && tn.wgrad_dma < 2);
-    if (dma) {
-        if (big) {       // re-derive the split for the 128x128 tile
-            tiles = cdiv(d.Cout, 128) * cdiv(d.K, 128);
-            splits = cdiv(slots_env_, tiles);
-            if (splits > slabs / 4) splits = slabs / 4;
-            if (splits < 1) splits = 1;
-            slabs_per = cdiv(slabs, splits);
-            d.pix_per_split = slabs_per * bp;
-            splits = cdiv(d.M, d.pix_per_split);
-            grid = dim3(cdiv(d.Cout, 128), cdiv(d.K, 128), splits);
-        }
-        if (!dry) hipLaunchKernelGGL((wgrad_bf16_dma_kernel<128, 128, 2, 2>), grid, dim3(256), 0, st, d);
-        which = "wgrad_bf16_dma";
-    } else if (big || lean) {
-        if (ordered) plan_ordered(d, big, ws, fin);
-        if (!ws.fits()) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad: workspace too small (aldi_conv_wgrad_group_workspace)");
-        if (!dry) {
-            if (big && (tn.wgrad_dma64 & 1)) { if (tn.wgrad_ilv) hipLaunchKernelGGL(wgrad_bf16_big64_kernel<true>, grid, dim3(512), 0, st, d); else hipLaunchKernelGGL(wgrad_bf16_big64_kernel<false>, grid, dim3(512), 0, st, d); }
-            else if (big) hipLaunchKernelGGL(wgrad_bf16_big_kernel, grid, dim3(512), 0, st, d);
-            else hipLaunchKernelGGL(wgrad_bf16_lean_kernel, grid, dim3(256), 0, st, d);
-        }
-        which = big ? ((tn.wgrad_dma64 & 1) ? "wgrad_bf16_big64" : "wgrad_bf16_big") : "wgrad_bf16_lean";
-    }
-    else if (a->dtype == ALDI_BF16) { if (!dry) hipLaunchKernelGGL(wgrad_bf16_kernel, grid, dim3(256), 0, st, d); which = "wgrad_bf16_generic"; }
-    else if (a->dtype == ALDI_F32 && f32_t128) { if (!dry) hipLaunchKernelGGL(wgrad_f32_t128_kernel<32>, grid, dim3(256), 0, st, d); which = "wgrad_f32_t128"; }
-    else if (a->dtype == ALDI_F32) { if (!dry) hipLaunchKernelGGL(wgrad_f32_kernel, grid, dim3(256), 0, st, d); which = "wgrad_f32"; }
-    else return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad: bad dtype");
-    if (dry) return ALDI_OK;
-    ALDI_CHECK_LAUNCH();
-    if (a->db && (dma || !(big || lean)))           // only the lean / 256x256 kernels add the bias gradient themselves
-        if (int rc = aldi_bias_grad(a->g, a->db, d.M, d.Cout, a->dtype, st)) return rc;
-    {
-        char name[96];
-        snprintf(name, sizeof(name), "%s splits=%d%s", which, splits, d.ordered ? " ordered" : "");
-        aldi_note_dispatch(name);
-    }
-    return ALDI_OK;
-}
-
-// one grouped launch of the problems idx[0..ng) with a common pixel length per workgroup; big: 256x256 tiles, one workgroup per CU
-int launch_group(const WgDev* probs, int ng, bool big, hipStream_t st, WsCarver& ws, FinBuilder& fin, bool ordered, bool dry, char* name, size_t name_len) {
-    const AldiTuning& tn = aldi_tuning();
-    const int tile = big ? 256 : 128;
-    long tiles_of[kMaxGroup];
-    int order[kMaxGroup];
-    long maxM = 0;
-    for (int i = 0; i < ng; ++i) {
-        tiles_of[i] = (long)cdiv(probs[i].Cout, tile) * cdiv(probs[i].K, tile);
-        if (probs[i].M > maxM) maxM = probs[i].M;
-        order[i] = i;
-    }
-    auto wgs_for = [&](long T) {
-        long w = 0;
-        for (int i = 0; i < ng; ++i) w += tiles_of[i] * cdiv(probs[i].M, T);
-        return w;
-    };
-    // Pixels per workgroup: ONE value T for the whole group (workgroups of equal length), chosen by a round model.  128x128: three
-    // workgroups are resident per CU (168 VGPRs) and need each other to hide their LDS / DMA latency, so the chip works through
-    // the launch in rounds of 768, a round lasting (T / 32 slab steps + one epilogue of ~wgrad_group_epi slab steps).  Measured on
-    // the step's groups: 392 unsplit res4 tiles 603 us, three splits (1176 workgroups) 544 us; one 256-workgroup round of res3
-    // 553 us against 432 us for 512 half-length workgroups.  256x256: one workgroup per CU, rounds of wgrad_big_slots.
-    long T = (maxM + 63) / 64 * 64;
-    const long target = big ? 0 : tn.wgrad_group_slots;
-    if (target > 0) {
-        while (T > 256 && wgs_for(T) < target) T = (T / 2 + 63) / 64 * 64;   // >= 4 slabs behind every epilogue
-    } else {
-        const long slots = big ? (tn.wgrad_big_slots > 0 ? tn.wgrad_big_slots : 256) : 768;
-        const long epi = big ? tn.wgrad_big_epi : tn.wgrad_group_epi;
-        const long minT = big ? 512 : 256;
-        long best = -1;
-        for (int sp = 1; sp <= 4096; ++sp) {
-            const long Ts = ((maxM + sp - 1) / sp + 63) / 64 * 64;
-            if (Ts < minT && sp > 1) break;
-            const long rounds = (wgs_for(Ts) + slots - 1) / slots;
-            const long cost = rounds * (Ts / 32 + epi);
-            if (best < 0 || cost < best) { best = cost; T = Ts; }
-        }
-    }
-    // longest-running problems first (K x K convs before 1x1: more k-steps per pixel do not matter, pixels per workgroup do)
-    for (int i = 1; i < ng; ++i)
-        for (int j = i; j > 0 && probs[order[j]].M > probs[order[j - 1]].M; --j) { int t_ = order[j]; order[j] = order[j - 1]; order[j - 1] = t_; }
-    static thread_local WgGroup L_;
-    L_.n = ng;
-    int wg = 0;
-    for (int k = 0; k < ng; ++k) {
-        WgDev d = probs[order[k]];
-        d.pix_per_split = (int)(T < d.M ? T : (d.M + 63) / 64 * 64);
-        d.splits = cdiv(d.M, d.pix_per_split);
-        if (ordered && d.ordered >= 0) plan_ordered(d, big, ws, fin);
-        else d.ordered = 0;
-        L_.p[k] = d;
-        L_.gx[k] = cdiv(d.Cout, tile);
-        L_.gy[k] = cdiv(d.K, tile);
-        L_.gz[k] = d.splits;
-        L_.wg_begin[k] = wg;
-        wg += L_.gx[k] * L_.gy[k] * L_.gz[k];
-    }
-    if (!ws.fits()) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad_group: workspace too small (aldi_conv_wgrad_group_workspace)");
-    for (int k = ng; k <= kMaxGroup; ++k) L_.wg_begin[k] = wg;
-    if (dry) return ALDI_OK;
-    // wgrad_dma64 bit 2: the 128 x 128 group on the LDS-DMA + transpose-read loop when every layer's rows are whole 16-byte chunks
-    bool lean64 = !big && (tn.wgrad_dma64 & 2);
-    for (int k = 0; k < ng && lean64; ++k) lean64 = L_.p[k].Cin % 8 == 0 && L_.p[k].Cout % 8 == 0;
-    if (big && (tn.wgrad_dma64 & 1)) { if (tn.wgrad_ilv) hipLaunchKernelGGL(wgrad_bf16_big64_group_kernel<true>, dim3(wg), dim3(512), 0, st, L_); else hipLaunchKernelGGL(wgrad_bf16_big64_group_kernel<false>, dim3(wg), dim3(512), 0, st, L_); }
-    else if (big) hipLaunchKernelGGL(wgrad_bf16_big_group_kernel, dim3(wg), dim3(512), 0, st, L_);
-    else if (lean64) { if (tn.wgrad_ilv) hipLaunchKernelGGL(wgrad_bf16_lean64_group_kernel<true>, dim3(wg), dim3(256), 0, st, L_); else hipLaunchKernelGGL(wgrad_bf16_lean64_group_kernel<false>, dim3(wg), dim3(256), 0, st, L_); }
-    else if (tn.wgrad_db) hipLaunchKernelGGL(wgrad_bf16_lean_group_db_kernel, dim3(wg), dim3(256), 0, st, L_);
-    else hipLaunchKernelGGL(wgrad_bf16_lean_group_kernel, dim3(wg), dim3(256), (size_t)tn.wgrad_lds_pad_kb << 10, st, L_);
-    ALDI_CHECK_LAUNCH();
-    snprintf(name, name_len, "wgrad_bf16_%s_group%s n=%d wgs=%d pix=%ld%s", big ? ((tn.wgrad_dma64 & 1) ? "big64" : "big") : (lean64 ? "lean64" : "lean"), (!big && tn.wgrad_db) ? "_db" : "", ng, wg, T, ordered ? " ordered" : "");
-    return ALDI_OK;
-}
-
-int wgrad_group_impl(const aldi_wgrad_args* args, int n, hipStream_t st, bool dry, size_t* need) {
-    if (!args || n < 1) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad_group: no problems");
-    const AldiTuning& tn = aldi_tuning();
-    const bool ordered = dry || (args[0].ws != nullptr && tn.wgrad_ordered);
-    WsCarver ws{static_cast<float*>(args[0].ws), dry ? 0 : (size_t)args[0].ws_bytes / 4, 0, dry};
-    FinBuilder fin(st, dry);
-    // problems the lean / 256x256 kernels cannot take (fp32, strided, unpadded ...) go through the single-problem dispatcher
-    static thread_local WgDev lean_p[kMaxGroup], big_p[kMaxGroup];
-    int nl = 0, nb = 0;
-    for (int i = 0; i < n; ++i) {
-        WgDev d;
-        if (int rc = fill_wgdev(&args[i], d)) return rc;
-        // layers that SHARE a gradient buffer inside one call (one conv applied to several pyramid levels) would race in the plain
-        // read-modify-write / second pass: those keep the float-atomic epilogue
-        bool shared = false;
-        for (int j = 0; j < n && !shared; ++j)
-            shared = j != i && (args[j].dw == args[i].dw || (args[i].db && args[j].db == args[i].db));
-        const bool elig = lean_eligible(&args[i], d) && tn.wgrad_lean;
-        const bool big_group = elig && tn.wgrad_big_group && d.Cout % 256 == 0 && d.K % 256 == 0 && d.M >= 512 && nb < kMaxGroup;
-        if (!elig || (!big_group && (nl == kMaxGroup || wants_big_tile(d, tn)))) {      // (alone, the big tile has its own launch)
-            if (int rc = wgrad_single(&args[i], st, ws, fin, ordered && !shared, dry)) return rc;
-            continue;
-        }
-        d.dbg = tn.wgrad_dbg;
-        d.xcd = tn.wgrad_xcd;
-        d.splits = 1; d.ordered = shared ? -1 : 0; d.ws = d.wsb = nullptr;
-        if (big_group) big_p[nb++] = d; else lean_p[nl++] = d;
-    }
-    if (nb) {
-        // a 256x256 launch wants a CU-count of workgroups with >= 1000 pixels each; a couple of tiles would be cut into hundreds of
-        // short pixel ranges (each ending in a 256-KB partial tile) just to occupy the chip: those layers stay with the 128x128 group
-        double tile_pixels = 0.0;
-        for (int i = 0; i < nb; ++i) tile_pixels += (double)(big_p[i].Cout / 256) * (big_p[i].K / 256) * big_p[i].M;
-        if (tile_pixels < 4096.0 * tn.wgrad_big_group_min && nl + nb <= kMaxGroup) {
-            for (int i = 0; i < nb; ++i) lean_p[nl++] = big_p[i];
-            nb = 0;
-        }
-    }
-    char nb_name[96] = "", nl_name[96] = "";
-    if (nb) if (int rc = launch_group(big_p, nb, true, st, ws, fin, ordered, dry, nb_name, sizeof(nb_name))) return rc;
-    if (nl) if (int rc = launch_group(lean_p, nl, false, st, ws, fin, ordered, dry, nl_name, sizeof(nl_name))) return rc;
-    fin.flush();
-    if (need) *need = ws.used * 4;
-    if (!dry && (nb || nl)) {
         ALDI_CHECK_LAUNCH();
-        char name[200];
-        snprintf(name, sizeof(name), "%s%s%s", nl_name, (nb && nl) ? " | " : "", nb_name);
-        aldi_note_dispatch(name);
+        if (L.bias_pass)
+            if (int rc = aldi_bias_grad(d.g, d.db, d.M, d.Cout, L.dtype, st)) return rc;
     }
+    // the second pass of the ordered epilogue: every producer of the call has been launched
+    for (size_t i0 = 0; i0 < P.fin.size(); i0 += kMaxGroup) {
+        WgFin F;
+        F.n = (int)(P.fin.size() - i0 < (size_t)kMaxGroup ? P.fin.size() - i0 : kMaxGroup);
+        int wg = 0;
+        for (int k = 0; k <= kMaxGroup; ++k) {
+            F.wg_begin[k] = wg;
+            if (k < F.n) { F.it[k] = P.fin[i0 + k]; wg += fin_workgroups(F.it[k]); }
+        }
+        hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(wg), dim3(256), 0, st, F);
+        ALDI_CHECK_LAUNCH();
+    }
+    char name[200];
+    dispatch_name(P, name, sizeof(name));
+    aldi_note_dispatch(name);
     return ALDI_OK;
 }
+
 }  // namespace
 
 extern "C" int aldi_conv_wgrad_group(const aldi_wgrad_args* args, int n, aldi_stream_t stream) {
-    return wgrad_group_impl(args, n, static_cast<hipStream_t>(stream), false, nullptr);
+    WgPlan& P = plan_storage();
+    if (int rc = plan_wgrad(args, n, true, false, aldi_tuning(), P)) return rc;
+    return execute_plan(P, static_cast<hipStream_t>(stream));
 }
-extern "C" long aldi_conv_wgrad_group_workspace(const aldi_wgrad_args* args, int n) {
-    size_t need = 0;
-    if (wgrad_group_impl(args, n, nullptr, true, &need)) return -1;
-    if (n == 1) {
-        // one problem may be handed to aldi_conv_wgrad instead, whose dispatcher splits the pixels by its own rule (knob wgrad_slots): the larger of the two
-        WsCarver ws{nullptr, 0, 0, true};
-        FinBuilder fin(nullptr, true);
-        if (wgrad_single(&args[0], nullptr, ws, fin, true, true)) return -1;
-        if (ws.used * 4 > need) need = ws.used * 4;
-    }
-    return (long)need;
-}
+extern "C" long aldi_conv_wgrad_group_workspace(const aldi_wgrad_args* args, int n) { return workspace_bytes(args, n, aldi_tuning(), plan_storage()); }
 
 extern "C" int aldi_conv_wgrad(const aldi_wgrad_args* a, aldi_stream_t stream) {
-    if (!a) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_wgrad: null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool ordered = a->ws != nullptr && aldi_tuning().wgrad_ordered;
-    WsCarver ws{static_cast<float*>(a->ws), (size_t)a->ws_bytes / 4, 0, false};
-    FinBuilder fin(st, false);
-    if (int rc = wgrad_single(a, st, ws, fin, ordered, false)) return rc;
-    fin.flush();
-    ALDI_CHECK_LAUNCH();
+    WgPlan& P = plan_storage();
+    if (int rc = plan_wgrad(a, 1, false, false, aldi_tuning(), P)) return rc;
+    return execute_plan(P, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int aldi_conv_wgrad_plan(const aldi_wgrad_args* args, int n, int group, char* name, int cap, long* ws_bytes) {
+    WgPlan& P = plan_storage();
+    if (int rc = plan_wgrad(args, n, group != 0, false, aldi_tuning(), P)) return rc;
+    char buf[200];
+    dispatch_name(P, buf, sizeof(buf));
+    if (ws_bytes && (*ws_bytes = workspace_bytes(args, group ? n : 1, aldi_tuning(), P)) < 0) return ALDI_ERR_ARG;
+    if (name && cap > 0) snprintf(name, (size_t)cap, "%s", buf);
     return ALDI_OK;
 }
 

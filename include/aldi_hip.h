@@ -195,6 +195,13 @@ int aldi_conv_wgrad_group(const aldi_wgrad_args* args, int n, aldi_stream_t stre
  * Layers whose Cout and K are multiples of 256 (knob wgrad_big_group, default 1) are launched together as 256x256 tiles, about one
  * workgroup per CU (knob wgrad_big_epi: cost of one epilogue in 32-pixel steps in the split model), the others as 128x128 tiles. */
 long aldi_conv_wgrad_group_workspace(const aldi_wgrad_args* args, int n);
+/* Dry run: what aldi_conv_wgrad(args) (group == 0; n is ignored) or aldi_conv_wgrad_group(args, n) (group != 0) would launch for these
+ * arguments under the current tuning knobs.  It plans exactly as the launch does -- args[0].ws null means the float-atomic epilogue, a too
+ * small args[0].ws_bytes is the launch's error -- with the same argument checks, status and error text, and writes the name
+ * aldi_last_dispatch() would report afterwards to name[cap] (truncated to cap; name may be null).  ws_bytes (nullable) receives what
+ * aldi_conv_wgrad_group_workspace answers for the same call.  Launches nothing, needs no GPU, leaves aldi_last_dispatch() alone, and never
+ * dereferences a tensor pointer: only which of them are null or equal matters. */
+int aldi_conv_wgrad_plan(const aldi_wgrad_args* args, int n, int group, char* name, int cap, long* ws_bytes);
 
 /* db[c] += sum_m g[m][c] (bias gradients), g is [M][C] in `dtype`. */
 int aldi_bias_grad(const void* g, float* db, int M, int C, int dtype, aldi_stream_t stream);

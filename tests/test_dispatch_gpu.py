@@ -12,6 +12,8 @@ References (what the reference reaches through detectron2: aldi/trainer.py:87 fo
   * the whole tensor against fp32 library GEMMs on the GPU (torch.matmul -> hipBLASLt, one per tap on shifted
     views: an independent implementation) -- catches a wrong border mask anywhere in the tensor.
 """
+import re
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -598,6 +600,50 @@ def test_wgrad_group_layers_sharing_one_gradient_buffer():
     assert (dw.double() - ref).abs().max().item() <= 3e-5 * ref.abs().max().item()
     assert (db.double() - refb).abs().max().item() <= 3e-5 * refb.abs().max().item()
     assert (other.double() - _wgrad_ref(x, g, 1, 1, 0)).abs().max().item() <= 3e-5 * other.abs().max().item()
+
+
+def test_wgrad_finalize_pass_follows_every_producer_of_the_call():
+    """more problems than one group launch takes (24): the rest goes through ordered, split single launches, and with the group's split members
+    the call has more finalize items than one finalize launch takes.  Every finalize launch has to FOLLOW every producer of the call: a finalize
+    pass that runs when its table is full -- before the group kernel -- adds whatever the workspace held (here: NaN) into dw.
+    x and g hold small integers, so every partial sum is exact in fp32 and a result does not depend on how its pixels were split (64 ranges in
+    the single launches, 10 in the group): all 26 gradients are the same bits."""
+    from aldi_amd import _lib as L
+    from aldi_amd import ops
+    n, (N, H, W_, Cin, Cout) = 26, (4, 64, 64, 256, 256)
+    gen = torch.Generator().manual_seed(31)
+    x = torch.randint(-3, 4, (N, H, W_, Cin), generator=gen).to("cuda", torch.bfloat16)
+    g = torch.randint(-3, 4, (N, H, W_, Cout), generator=gen).to("cuda", torch.bfloat16)
+    dw0 = torch.randn(Cout, 1, 1, Cin, generator=gen).to("cuda")
+    dws = [dw0.clone() for _ in range(n)]
+    L.set_tuning("wgrad_big_min", 1)
+    # the condition, from the plan (no launch): 24 members of one 256x256 group, each in several pixel ranges, behind two ordered split single launches
+    arr = (L.WgradArgs * n)(*[L.WgradArgs(x.data_ptr(), g.data_ptr(), dw.data_ptr(), None, N, H, W_, Cin, Cout, 1, 1, 1, 0, H, W_, L.BF16, None, None, 0) for dw in dws])
+    arr[0].ws, arr[0].ws_bytes = x.data_ptr(), 1 << 40              # (any non-null address: the plan does not touch it)
+    name, _ = L.plan_wgrad_dispatch(arr, n, group=True)
+    m = re.fullmatch(r"wgrad_bf16_big64_group n=(\d+) wgs=\d+ pix=(\d+) ordered", name)
+    assert m, name
+    members, pix = int(m.group(1)), int(m.group(2))
+    single, _ = L.plan_wgrad_dispatch(arr, 1, group=False)           # what the problems past the 24th get (forwarded singles launch before the groups)
+    ms = re.fullmatch(r"wgrad_bf16_big64 splits=(\d+) ordered", single)
+    assert ms and int(ms.group(1)) > 1, single
+    assert members == 24 and pix < N * H * W_ and n - members >= 1, (name, single)      # finalize items: (n - members) + members = 26 > 24
+    probs = [(x, g, dw, dict(KH=1, KW=1, stride=1, pad=0)) for dw in dws]
+    ops.conv_wgrad_group(probs)                                      # sizes the workspace
+    torch.cuda.synchronize()
+    for buf in ops._WGRAD_WS.values():
+        buf.fill_(float("nan"))
+    for dw in dws:
+        dw.copy_(dw0)
+    ops.conv_wgrad_group(probs)
+    assert L.last_dispatch() == name
+    torch.cuda.synchronize()
+    ref = dw0.double() + _wgrad_ref(x, g, 1, 1, 0)
+    M = N * H * W_
+    bad = [i for i, dw in enumerate(dws) if not torch.equal(dw, dws[0])]
+    assert not bad, (len(bad), bad, [int(torch.isnan(dws[i]).sum()) for i in bad])
+    e = (dws[0].double() - ref).abs().max().item()
+    assert e <= 3e-6 * max(1.0, ref.abs().max().item()) * max(1.0, (M / 1024) ** 0.5), e
 
 
 @pytest.mark.parametrize("slots", [0, 1, 4000])
