@@ -16,6 +16,7 @@
 //             read in place (no im2col); W2 streams tap by tap through a four-stage ring.  a2 -> LDS [128 px][64 ch].
 //   phase 3   y = relu(W3 a2 + b3 + r): [256 co] x [128 px] x 64, W3 (32 KB) is DMA'd into the dead tap ring under the a2 epilogue; the
 //             result goes through an LDS staging tile so that residual loads and stores are 16 B per lane, 512 B per pixel row.
+//             (The stage's first block, SC form: r is the projection shortcut, computed here from x -- see bneck_kernel.)
 // Four waves per workgroup, 78 KB of LDS: two workgroups per CU, so one's HBM phases (x slabs, residual, stores) run beside the
 // other's MFMA phases.  Weights: the accumulator fragment's A operand (lane = 4 consecutive output channels of one pixel).
 //
@@ -40,6 +41,7 @@ struct BneckDev {
     const bf16_t* x; const bf16_t* res; bf16_t* y;
     const bf16_t* w1; const bf16_t* w2; const bf16_t* w3;
     const float* b1; const float* b2; const float* b3;
+    const bf16_t* wsc; const float* ssc; const float* bsc;       // SC: the projection shortcut's weights [256][64], FrozenBN scale / shift
     int N, H, W, th, tw, xcd;
     unsigned x_bytes, y_bytes;
 };
@@ -62,9 +64,17 @@ __device__ __forceinline__ uint2 relu_pack4(f32x4_t a, float4 sh, bool keep) {
     return t;
 }
 
-template <int CX>
+// SC: the stage's first block.  The residual is the projection shortcut bf16((Wsc . x) * scale + shift) of the tile's own 128 centre pixels,
+// formed in phase 3 instead of read from memory: the pixels come again (L2-hot, 16 KB by LDS-DMA beside W3) into the dead a1 region, this
+// wave's Wsc fragments (64 channels x 64 k) sit in registers.  Per output element the same two MFMA k-steps in the same order and the same
+// fp32 scale / shift / single rounding as the 1x1 launch it replaces (igemm_ws.h), so the block's output is bit for bit that of the
+// two-launch path.  Phase 3 then runs in two halves of 32 channels per wave (shortcut GEMM, main GEMM, combine): 64 accumulator
+// registers live instead of 2 x 128, and the finished bf16 values wait in registers until a2 / W3 / x are dead and the staging tile may
+// cover them.
+template <int CX, bool SC>
 __global__ __launch_bounds__(256, 2) void bneck_kernel(BneckDev p) {
     static_assert(CX % 32 == 0, "x slabs of 32 channels");
+    static_assert(!SC || CX == 64, "the shortcut's x tile is one 128-byte row per pixel");
     __shared__ __attribute__((aligned(128))) uint4 lds[kLdsBytes / 16];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fq = lane >> 4;
@@ -93,6 +103,19 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(BneckDev p) {
         sh1[j] = *reinterpret_cast<const float4*>(p.b1 + j * 16 + fq * 4);
         sh2[j] = *reinterpret_cast<const float4*>(p.b2 + j * 16 + fq * 4);
         sh3[j] = *reinterpret_cast<const float4*>(p.b3 + (wave * 4 + j) * 16 + fq * 4);
+    }
+    // SC: Wsc as A fragments (row = channel (wave * 4 + j) * 16 + fr, k = ks * 32 + fq * 8 .. + 7) and the shortcut's scale / shift
+    u32x4_t wscf[SC ? 4 : 1][2];
+    float4 ssc[SC ? 4 : 1], bsc[SC ? 4 : 1];
+    if constexpr (SC) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+                wscf[j][ks] = *reinterpret_cast<const u32x4_t*>(p.wsc + ((wave * 4 + j) * 16 + fr) * MID + ks * 32 + fq * 8);
+            ssc[j] = *reinterpret_cast<const float4*>(p.ssc + (wave * 4 + j) * 16 + fq * 4);
+            bsc[j] = *reinterpret_cast<const float4*>(p.bsc + (wave * 4 + j) * 16 + fq * 4);
+        }
     }
 
     // ---------------------------------------------------------------------------------------------------- phase 1
@@ -236,6 +259,15 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(BneckDev p) {
         const int c = tid + it * 256, row = c >> 3, q = c & 7;
         glds16(rw3, &lds[kRegA / 16 + wbase + it * 256], (unsigned)((row * MID + (q ^ ((row >> 1) & 7)) * 8) * 2));
     }
+    if constexpr (SC) {                              // the tile's 8 x 16 centre pixels of x, laid out like a2, into the dead a1 region
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int c = tid + it * 256, row = c >> 3, q = c & 7;
+            const int gh = h0 + (row >> 4), gw = w0 + (row & 15);
+            const bool ok = gh < p.H && gw < p.W;
+            glds16(rx, &lds[kRegB / 16 + wbase + it * 256], ok ? (unsigned)(((img_pix + (long)gh * p.W + gw) * CX + (q ^ ((row >> 1) & 7)) * 8) * 2) : OOB);
+        }
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = (wave * 2 + i) * 16 + fr;
@@ -249,43 +281,116 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(BneckDev p) {
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     // ---------------------------------------------------------------------------------------------------- phase 3
-    f32x4_t acc3[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc3[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        const int sw = (ks * 4 + fq) ^ ((fr >> 1) & 7);
-        const unsigned ab = lbase + kRegC + (unsigned)((fr * 8 + sw) * 16);
-        const unsigned w3b = lbase + kRegA + (unsigned)(((wave * 64 + fr) * 8 + sw) * 16);
-        u32x4_t af[8], wf[4];
-        frag_read_all<8, 128>(af, ab);
-        frag_read_all<4, 128>(wf, w3b);
-        frag_wait<8, 4>(af, wf);
-#pragma unroll
+    if constexpr (!SC) {
+        f32x4_t acc3[8][4];
+    #pragma unroll
         for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc3[i][j] = Mma<bf16_t>::run(wf[j], af[i], acc3[i][j]);
-    }
-    __builtin_amdgcn_s_barrier();                    // a2 / W3 are dead: the staging tile covers them
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int co = (wave * 4 + j) * 16 + fq * 4;
-        const float4 sh = sh3[j];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            uint2 t;
-            t.x = pack2_bf16(acc3[i][j][0] + sh.x, acc3[i][j][1] + sh.y);
-            t.y = pack2_bf16(acc3[i][j][2] + sh.z, acc3[i][j][3] + sh.w);
-            lds_write_b64(lbase + (unsigned)((i * 16 + fr) * kStgRow + co * 2), t);
+    #pragma unroll
+            for (int j = 0; j < 4; ++j) acc3[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    #pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const int sw = (ks * 4 + fq) ^ ((fr >> 1) & 7);
+            const unsigned ab = lbase + kRegC + (unsigned)((fr * 8 + sw) * 16);
+            const unsigned w3b = lbase + kRegA + (unsigned)(((wave * 64 + fr) * 8 + sw) * 16);
+            u32x4_t af[8], wf[4];
+            frag_read_all<8, 128>(af, ab);
+            frag_read_all<4, 128>(wf, w3b);
+            frag_wait<8, 4>(af, wf);
+    #pragma unroll
+            for (int i = 0; i < 8; ++i)
+    #pragma unroll
+                for (int j = 0; j < 4; ++j) acc3[i][j] = Mma<bf16_t>::run(wf[j], af[i], acc3[i][j]);
         }
+        __builtin_amdgcn_s_barrier();                    // a2 / W3 are dead: the staging tile covers them
+        __builtin_amdgcn_sched_barrier(0);
+    #pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int co = (wave * 4 + j) * 16 + fq * 4;
+            const float4 sh = sh3[j];
+    #pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                uint2 t;
+                t.x = pack2_bf16(acc3[i][j][0] + sh.x, acc3[i][j][1] + sh.y);
+                t.y = pack2_bf16(acc3[i][j][2] + sh.z, acc3[i][j][3] + sh.w);
+                lds_write_b64(lbase + (unsigned)((i * 16 + fr) * kStgRow + co * 2), t);
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    } else {
+        uint2 outp[8][4];                            // the finished block output of this lane's (pixel block i, channel block j) quads
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            f32x4_t acc[8][2];
+            uint2 scp[8][2];
+            // the shortcut: [32 co] x [128 px] x 64, then bf16(acc * scale + shift) as the separate launch stored it
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const int sw = (ks * 4 + fq) ^ ((fr >> 1) & 7);
+                u32x4_t xf[8];
+                frag_read_all<8, 128>(xf, lbase + kRegB + (unsigned)((fr * 8 + sw) * 16));
+                frag_wait<8, 0>(xf, xf);
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+#pragma unroll
+                    for (int jj = 0; jj < 2; ++jj)
+                        acc[i][jj] = Mma<bf16_t>::run(wscf[hf * 2 + jj][ks], xf[i], ks == 0 ? f32x4_t{0.f, 0.f, 0.f, 0.f} : acc[i][jj]);
+            }
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+                const float4 sc = ssc[hf * 2 + jj], sh = bsc[hf * 2 + jj];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    float v0 = acc[i][jj][0] * sc.x, v1 = acc[i][jj][1] * sc.y, v2 = acc[i][jj][2] * sc.z, v3 = acc[i][jj][3] * sc.w;
+                    v0 += sh.x; v1 += sh.y; v2 += sh.z; v3 += sh.w;
+                    scp[i][jj].x = pack2_bf16(v0, v1);
+                    scp[i][jj].y = pack2_bf16(v2, v3);
+                }
+            }
+            // conv3 on the same channels
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const int sw = (ks * 4 + fq) ^ ((fr >> 1) & 7);
+                u32x4_t af[8], wf[2];
+                frag_read_all<8, 128>(af, lbase + kRegC + (unsigned)((fr * 8 + sw) * 16));
+                frag_read_all<2, 128>(wf, lbase + kRegA + (unsigned)(((wave * 64 + hf * 32 + fr) * 8 + sw) * 16));
+                frag_wait<8, 2>(af, wf);
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+#pragma unroll
+                    for (int jj = 0; jj < 2; ++jj)
+                        acc[i][jj] = Mma<bf16_t>::run(wf[jj], af[i], ks == 0 ? f32x4_t{0.f, 0.f, 0.f, 0.f} : acc[i][jj]);
+            }
+            // y = relu(bf16(acc + b3) + shortcut): the rounding the staging tile gives the sum in the residual form, then the same add
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj) {
+                const float4 sh = sh3[hf * 2 + jj];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const unsigned s0 = pack2_bf16(acc[i][jj][0] + sh.x, acc[i][jj][1] + sh.y), s1 = pack2_bf16(acc[i][jj][2] + sh.z, acc[i][jj][3] + sh.w);
+                    const unsigned r0 = scp[i][jj].x, r1 = scp[i][jj].y;
+                    outp[i][hf * 2 + jj].x = pack2_bf16(fmaxf(__uint_as_float(s0 << 16) + __uint_as_float(r0 << 16), 0.f),
+                                                        fmaxf(__uint_as_float(s0 & 0xffff0000u) + __uint_as_float(r0 & 0xffff0000u), 0.f));
+                    outp[i][hf * 2 + jj].y = pack2_bf16(fmaxf(__uint_as_float(s1 << 16) + __uint_as_float(r1 << 16), 0.f),
+                                                        fmaxf(__uint_as_float(s1 & 0xffff0000u) + __uint_as_float(r1 & 0xffff0000u), 0.f));
+                }
+            }
+        }
+        __builtin_amdgcn_s_barrier();                // a2 / W3 / x are dead: the staging tile covers them
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int co = (wave * 4 + j) * 16 + fq * 4;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) lds_write_b64(lbase + (unsigned)((i * 16 + fr) * kStgRow + co * 2), outp[i][j]);
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
     // y = relu(staged + residual): a lane finishes 16 B of one pixel, a wave instruction two whole pixel rows (2 x 512 B)
+    // (SC: the staged values are finished, they only change layout)
     {
         const __amdgpu_buffer_rsrc_t rr = make_rsrc_uniform(p.res, p.y_bytes);
         const __amdgpu_buffer_rsrc_t ry = make_rsrc_uniform(p.y, p.y_bytes);
@@ -299,8 +404,10 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(BneckDev p) {
             const bool ok = gh < p.H && gw < p.W;
             goff[it] = ok ? (unsigned)(((img_pix + (long)gh * p.W + gw) * CO + ch * 8) * 2) : OOB;
         }
+        if constexpr (!SC) {
 #pragma unroll
-        for (int it = 0; it < NI; ++it) rres[it] = __builtin_amdgcn_raw_buffer_load_b128(rr, goff[it], 0, 0);
+            for (int it = 0; it < NI; ++it) rres[it] = __builtin_amdgcn_raw_buffer_load_b128(rr, goff[it], 0, 0);
+        }
         u32x4_t sv[NI];
         stg_read_all<NI, 8 * kStgRow>(sv, lbase + (unsigned)((tid >> 5) * kStgRow + (tid & 31) * 16));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -308,12 +415,14 @@ __global__ __launch_bounds__(256, 2) void bneck_kernel(BneckDev p) {
         for (int it = 0; it < NI; ++it) asm volatile("" : "+v"(sv[it]));
 #pragma unroll
         for (int it = 0; it < NI; ++it) {
-            u32x4_t ov;
+            u32x4_t ov = sv[it];
+            if constexpr (!SC) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float lo = fmaxf(__uint_as_float(sv[it][q] << 16) + __uint_as_float(rres[it][q] << 16), 0.f);
-                const float hi = fmaxf(__uint_as_float(sv[it][q] & 0xffff0000u) + __uint_as_float(rres[it][q] & 0xffff0000u), 0.f);
-                ov[q] = pack2_bf16(lo, hi);
+                for (int q = 0; q < 4; ++q) {
+                    const float lo = fmaxf(__uint_as_float(sv[it][q] << 16) + __uint_as_float(rres[it][q] << 16), 0.f);
+                    const float hi = fmaxf(__uint_as_float(sv[it][q] & 0xffff0000u) + __uint_as_float(rres[it][q] & 0xffff0000u), 0.f);
+                    ov[q] = pack2_bf16(lo, hi);
+                }
             }
             __builtin_amdgcn_raw_buffer_store_b128(ov, ry, goff[it], 0, 0);
         }
@@ -350,27 +459,39 @@ extern "C" int aldi_fold_weights_batch(const aldi_fold_item* items, int n_items,
     return ALDI_OK;
 }
 
-extern "C" int aldi_bottleneck_fused(const aldi_bottleneck_args* a, aldi_stream_t stream) {
-    if (!a || !a->x || !a->res || !a->y || !a->w1 || !a->w2 || !a->w3 || !a->b1 || !a->b2 || !a->b3)
+// one launcher for both entry points; wsc != nullptr: the shortcut form (no residual pointer)
+static int launch_bneck(const aldi_bottleneck_args* a, const void* wsc, const float* ssc, const float* bsc, aldi_stream_t stream) {
+    const bool sc = wsc != nullptr;
+    if (!a || !a->x || (!sc && !a->res) || !a->y || !a->w1 || !a->w2 || !a->w3 || !a->b1 || !a->b2 || !a->b3)
         return aldi_set_error_msg(ALDI_ERR_ARG, "bottleneck_fused: null pointer");
-    if (a->mid != MID || a->Cout != CO || (a->Cin != 64 && a->Cin != 256) || a->N < 1 || a->H < 1 || a->W < 1)
-        return aldi_set_error_msg(ALDI_ERR_ARG, "bottleneck_fused: built for Cin in {64, 256}, 64 mid channels, 256 output channels (res2)");
+    if (a->mid != MID || a->Cout != CO || (a->Cin != 64 && (sc || a->Cin != 256)) || a->N < 1 || a->H < 1 || a->W < 1)
+        return aldi_set_error_msg(ALDI_ERR_ARG, sc ? "bottleneck_fused_sc: built for 64 input, 64 mid and 256 output channels (res2.0)"
+                                                   : "bottleneck_fused: built for Cin in {64, 256}, 64 mid channels, 256 output channels (res2)");
     const size_t xb = (size_t)a->N * a->H * a->W * a->Cin * 2, yb = (size_t)a->N * a->H * a->W * CO * 2;
     if (xb >= 0x80000000ull || yb >= 0x80000000ull) return aldi_set_error_msg(ALDI_ERR_ARG, "bottleneck_fused: operand larger than 2 GiB (32-bit buffer offsets)");
     BneckDev d;
     d.x = static_cast<const bf16_t*>(a->x); d.res = static_cast<const bf16_t*>(a->res); d.y = static_cast<bf16_t*>(a->y);
     d.w1 = static_cast<const bf16_t*>(a->w1); d.w2 = static_cast<const bf16_t*>(a->w2); d.w3 = static_cast<const bf16_t*>(a->w3);
     d.b1 = a->b1; d.b2 = a->b2; d.b3 = a->b3;
+    d.wsc = static_cast<const bf16_t*>(wsc); d.ssc = ssc; d.bsc = bsc;
     d.N = a->N; d.H = a->H; d.W = a->W; d.th = cdiv(a->H, TH); d.tw = cdiv(a->W, TW);
     d.xcd = aldi_tuning().igemm_xcd;
     d.x_bytes = (unsigned)xb; d.y_bytes = (unsigned)yb;
     const int tiles = a->N * d.th * d.tw;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (a->Cin == 64) hipLaunchKernelGGL(bneck_kernel<64>, dim3(tiles), dim3(256), 0, st, d);
-    else hipLaunchKernelGGL(bneck_kernel<256>, dim3(tiles), dim3(256), 0, st, d);
+    if (sc) hipLaunchKernelGGL((bneck_kernel<64, true>), dim3(tiles), dim3(256), 0, st, d);
+    else if (a->Cin == 64) hipLaunchKernelGGL((bneck_kernel<64, false>), dim3(tiles), dim3(256), 0, st, d);
+    else hipLaunchKernelGGL((bneck_kernel<256, false>), dim3(tiles), dim3(256), 0, st, d);
     ALDI_CHECK_LAUNCH();
     char name[64];
-    snprintf(name, sizeof(name), "bottleneck_fused<bf16,%d,64,256>", a->Cin);
+    snprintf(name, sizeof(name), "bottleneck_fused<bf16,%d,64,256%s>", a->Cin, sc ? ",shortcut" : "");
     aldi_note_dispatch(name);
     return ALDI_OK;
+}
+
+extern "C" int aldi_bottleneck_fused(const aldi_bottleneck_args* a, aldi_stream_t stream) { return launch_bneck(a, nullptr, nullptr, nullptr, stream); }
+
+extern "C" int aldi_bottleneck_fused_sc(const aldi_bottleneck_args* a, const void* wsc, const float* sc_scale, const float* sc_shift, aldi_stream_t stream) {
+    if (!wsc || !sc_scale || !sc_shift) return aldi_set_error_msg(ALDI_ERR_ARG, "bottleneck_fused_sc: null pointer");
+    return launch_bneck(a, wsc, sc_scale, sc_shift, stream);
 }

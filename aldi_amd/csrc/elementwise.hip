@@ -219,12 +219,23 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(StemDev p) {
 
 // Stem + max-pool in one kernel (bf16).  Unfused, the 7x7/2 conv writes its [N][400][672][64] map (206 MB for the step's six
 // images) only for the 3x3/2 max-pool to read it back; both kernels are then bound by that round trip and by the per-workgroup
-// weight conversion.  Here a workgroup produces a 7x7 tile of POOLED pixels: it computes the 16x16 tile of conv outputs that
-// starts one row / column before the first window (rows 2*py0-1 .. 2*py0+14: fifteen of them cover the seven windows; one conv row
-// per tile edge is computed twice), keeps it in LDS after FrozenBN + ReLU (-inf where the conv pixel lies outside the map: the
-// pool pads with -inf), and writes 16-B channel chunks of the 3x3 maxima.  Weights arrive pre-packed in the MFMA k order
-// (aldi_stem_pack_weights: once per weight refresh instead of 12 K scalar loads + conversions per workgroup).  Same MFMA sequence
-// per conv pixel as stem_mfma_kernel, so the result equals maxpool3s2(stem) bit for bit.
+// weight conversion.  Here a tile is 7x7 POOLED pixels: the 16x16 tile of conv outputs that starts one row / column before the
+// first window (rows 2*py0-1 .. 2*py0+14: fifteen of them cover the seven windows; one conv row per tile edge is computed twice) is
+// kept in LDS after FrozenBN + ReLU (-inf where the conv pixel lies outside the map: the pool pads with -inf), and 16-B channel
+// chunks of the 3x3 maxima are written.  Weights arrive pre-packed in the MFMA k order (aldi_stem_pack_weights: once per weight
+// refresh instead of 12 K scalar loads + conversions per workgroup).  Same MFMA sequence per conv pixel as stem_mfma_kernel, so the
+// result equals maxpool3s2(stem) bit for bit.
+//
+// PERSISTENT: a fixed grid (two workgroups per compute unit: 54 KB of LDS and <= 256 registers each) walks the tiles with a stride.
+//   * the packed weights are this lane's 24 MFMA A fragments, fetched ONCE per workgroup into registers (96 VGPRs) -- one workgroup per
+//     tile re-read the 25.6 KB weight image for every 49 pooled pixels (142 MB per N = 4 launch against 47 MB of image in + map out);
+//   * the uint8 tile comes as ALIGNED 4-byte loads (a thread owns 20 columns of one (channel, row): six words; the row start
+//     4*px0 - 5 is odd, the bytes are picked out of the words in registers) and goes to LDS in 8-byte writes;
+//   * double-buffered: the words of the NEXT tile are requested before this tile's MFMAs and converted into the other LDS image
+//     after them, so they fly under the MFMAs and the epilogue; two barriers per tile (conv tile written | pooled and next image
+//     written).  Tiles are independent: no flags, no waits between workgroups.
+// With the grid a multiple of 8 each XCD (workgroup id mod 8) walks one contiguous eighth of the tiles: neighbouring tiles share
+// 9 of their 37 input rows / columns in that XCD's L2.
 constexpr int kStemWK = 200;              // padded weight row (elements) of the packed [64][WK] bf16 image
 __global__ void stem_pack_kernel(const float* __restrict__ w, bf16_t* __restrict__ wpk) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -244,109 +255,195 @@ struct StemPoolDev {
     const bf16_t* wpk;
     bf16_t* yp;           // [N][Hp][Wp][64]
     int Hp, Wp;
+    int tiles_x, tiles_y, n_tiles;
 };
 
-__global__ __launch_bounds__(256) void stem_pool_mfma_kernel(StemPoolDev q) {
+constexpr int kStemPoolTH = 37, kStemPoolTW = 40, kStemPoolPT = 7;
+
+// Tile coordinates live in scalar registers: one division when the walk starts, carries after (the stride is split the same way)
+struct StemTile { int n, ty, tx; };
+__device__ __forceinline__ StemTile stem_tile(const StemPoolDev& q, int t) {
+    const int per = q.tiles_x * q.tiles_y;
+    StemTile r;
+    r.n = t / per;
+    const int rem = t - r.n * per;
+    r.ty = rem / q.tiles_x; r.tx = rem - r.ty * q.tiles_x;
+    r.n = __builtin_amdgcn_readfirstlane(r.n); r.ty = __builtin_amdgcn_readfirstlane(r.ty); r.tx = __builtin_amdgcn_readfirstlane(r.tx);
+    return r;
+}
+__device__ __forceinline__ StemTile stem_tile_advance(const StemPoolDev& q, StemTile a, const StemTile d) {
+    a.tx += d.tx;
+    if (a.tx >= q.tiles_x) { a.tx -= q.tiles_x; ++a.ty; }
+    a.ty += d.ty;
+    if (a.ty >= q.tiles_y) { a.ty -= q.tiles_y; ++a.n; }
+    a.n += d.n;
+    return a;
+}
+// the six aligned words that hold this thread's 20 input bytes of tile `tl` ((channel, row) tid >> 1, columns (tid & 1) * 20 .. + 19 of the
+// 37 x 40 image tile; byte k sits at offset 3 + k: the tile's first column 4*px0 - 5 is 3 mod 4).  A word outside the staging row is replaced by one inside it, a row outside the image by row 0: never a read outside the batch.
+__device__ __forceinline__ void stem_fetch(const StemPoolDev& q, const StemTile tl, const int tid, uint32_t (&raw)[6]) {
+    constexpr int TH = kStemPoolTH;
     const StemDev& p = q.s;
-    constexpr int TH = 37, TW = 40, WK = kStemWK, PT = 7, CS = 144;   // CS: bytes per conv pixel in the LDS conv tile (128 + pad)
-    constexpr int kWlBytes = 64 * WK * 2, kTileBytes = 3 * TH * TW * 2, kCtBytes = 256 * CS;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[(kWlBytes + kTileBytes) > kCtBytes ? (kWlBytes + kTileBytes) : kCtBytes];
-    bf16_t* wl = reinterpret_cast<bf16_t*>(smem);
-    bf16_t* tile = reinterpret_cast<bf16_t*>(smem + kWlBytes);
-    const int n = blockIdx.z;
-    const int py0 = blockIdx.y * PT, px0 = blockIdx.x * PT;
-    const int cy0 = 2 * py0 - 1, cx0 = 2 * px0 - 1;         // first conv pixel of the 16x16 tile
-    {   // packed weights: 1600 16-B chunks
-        const uint4* src = reinterpret_cast<const uint4*>(q.wpk);
-        uint4* dst = reinterpret_cast<uint4*>(wl);
-        for (int i = threadIdx.x; i < 64 * WK / 8; i += 256) dst[i] = src[i];
-    }
-    const int iy0 = cy0 * 2 - 3, ix0 = cx0 * 2 - 3;
-    const int h = p.h[n], w = p.wd[n];
-    {   // input tile: thread t copies 20 consecutive columns of one (channel, row)
-        const int r = threadIdx.x >> 1, half = threadIdx.x & 1;
-        if (r < 3 * TH) {
-            const int c = r / TH, yy = r - c * TH;
-            const int iy = iy0 + yy;
-            const bool rok = iy >= 0 && iy < h;
-            const uint8_t* row = p.img + (((long)n * 3 + c) * p.Hs + (rok ? iy : 0)) * p.Ws;
-            const float mean = p.mean[c], inv = p.inv_std[c];
+    const int r = tid >> 1, half = tid & 1;
+    const int c = r / TH, yy = r - c * TH;
+    const int iy = tl.ty * (4 * kStemPoolPT) - 5 + yy, x0 = tl.tx * (4 * kStemPoolPT) - 5 + half * 20 - 3;      // x0 % 4 == 0
+    const bool rok = r < 3 * TH && iy >= 0 && iy < p.h[tl.n];
+    const uint8_t* row = p.img + (((long)tl.n * 3 + (rok ? c : 0)) * p.Hs + (rok ? iy : 0)) * p.Ws;
 #pragma unroll
-            for (int k = 0; k < 20; ++k) {
-                const int xx = half * 20 + k, ix = ix0 + xx;
-                float v = 0.f;
-                if (rok && xx < TH && ix >= 0 && ix < w) v = ((float)row[ix] - mean) * inv;
-                tile[(c * TH + yy) * TW + xx] = f32_to_bf16(v);
+    for (int i = 0; i < 6; ++i) {                            // (clamped, not predicated: stem_convert drops every byte outside the image)
+        int x = x0 + 4 * i;
+        x = x < 0 ? 0 : (x > p.Ws - 4 ? p.Ws - 4 : x);
+        raw[i] = *reinterpret_cast<const uint32_t*>(row + x);
+    }
+}
+// (v - mean) * inv_std -> bf16 into the LDS image tile (zeros outside the image: the conv pads the NORMALISED image)
+__device__ __forceinline__ void stem_convert(const StemPoolDev& q, const StemTile tl, const int tid, const uint32_t (&raw)[6], bf16_t* tile) {
+    constexpr int TH = kStemPoolTH, TW = kStemPoolTW;
+    const StemDev& p = q.s;
+    const int r = tid >> 1, half = tid & 1;
+    if (r >= 3 * TH) return;
+    const int c = r / TH, yy = r - c * TH;
+    const int iy = tl.ty * (4 * kStemPoolPT) - 5 + yy, ix0 = tl.tx * (4 * kStemPoolPT) - 5;
+    const bool rok = iy >= 0 && iy < p.h[tl.n];
+    // this thread's bytes k with 0 <= ix < w and xx < TH (ix = ix0 + xx, xx = half * 20 + k): klo <= k < khi
+    const int xlim = p.wd[tl.n] - ix0 < TH ? p.wd[tl.n] - ix0 : TH;
+    const int klo = rok ? -ix0 - half * 20 : 20, khi = xlim - half * 20;
+    const float mean = p.mean[c], inv = p.inv_std[c];
+    uint2* dst = reinterpret_cast<uint2*>(tile + (c * TH + yy) * TW + half * 20);
+#pragma unroll
+    for (int g = 0; g < 5; ++g) {
+        bf16_t e[4];
+#pragma unroll
+        for (int k4 = 0; k4 < 4; ++k4) {
+            const int k = g * 4 + k4, b = 3 + k;
+            float v = 0.f;
+            if (k >= klo && k < khi) v = ((float)((raw[b >> 2] >> ((b & 3) * 8)) & 0xffu) - mean) * inv;
+            e[k4] = f32_to_bf16(v);
+        }
+        dst[g] = make_uint2((uint32_t)e[0] | ((uint32_t)e[1] << 16), (uint32_t)e[2] | ((uint32_t)e[3] << 16));
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void stem_pool_mfma_kernel(StemPoolDev q) {
+    const StemDev& p = q.s;
+    constexpr int TH = kStemPoolTH, TW = kStemPoolTW, WK = kStemWK, PT = kStemPoolPT, CS = 144;   // CS: bytes per conv pixel in the LDS conv tile (128 + pad)
+    constexpr int kTileBytes = (3 * TH * TW * 2 + 15) & ~15, kCtBytes = 256 * CS;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * kTileBytes + kCtBytes + 512];      // image tile 0 | image tile 1 | conv tile | scale, shift
+    unsigned char* ct = smem + 2 * kTileBytes;
+    float* bn = reinterpret_cast<float*>(smem + 2 * kTileBytes + kCtBytes);
+    if (threadIdx.x < 128) bn[threadIdx.x] = threadIdx.x < 64 ? p.scale[threadIdx.x] : p.shift[threadIdx.x - 64];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int fr = lane & 15, fq = lane >> 4;
+    // this workgroup's tiles: t0, t0 + step, ... < t_end
+    int t = blockIdx.x, step = gridDim.x, t_end = q.n_tiles;
+    if ((gridDim.x & 7) == 0) {
+        const int chunk = (q.n_tiles + 7) >> 3, xcd = blockIdx.x & 7;
+        t = xcd * chunk + (blockIdx.x >> 3); step = gridDim.x >> 3;
+        t_end = (xcd + 1) * chunk < q.n_tiles ? (xcd + 1) * chunk : q.n_tiles;
+    }
+    if (t >= t_end) return;
+    // the weights: A fragment (k-step s, channel block j) = row j * 16 + fr of the packed image, k = (s * 4 + fq) * 8 .. + 7
+    uint4 wf[6][4];
+    {
+        const uint4* wpk16 = reinterpret_cast<const uint4*>(q.wpk);
+#pragma unroll
+        for (int s = 0; s < 6; ++s)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) wf[s][j] = wpk16[((j * 16 + fr) * WK + (s * 4 + fq) * 8) >> 3];
+    }
+    StemTile cur = stem_tile(q, t);
+    const StemTile stride = stem_tile(q, step);
+    uint32_t raw[6];
+    stem_fetch(q, cur, threadIdx.x, raw);
+    stem_convert(q, cur, threadIdx.x, raw, reinterpret_cast<bf16_t*>(smem));
+    __syncthreads();
+    int buf = 0;
+    for (; t < t_end; t += step, buf ^= 1) {
+        const bool more = t + step < t_end;
+        // lane coordinates the compiler cannot see through: every address below is formed anew per tile from these three registers.  (Hoisted out
+        // of the tile loop they are ~50 loop-invariant registers beside the 96 of the weights, and the kernel spills.)
+        int tid_l = threadIdx.x, fr_l = fr, fq_l = fq;
+        asm volatile("" : "+v"(tid_l), "+v"(fr_l), "+v"(fq_l));
+        StemTile nxt = cur;
+        if (more) {
+            nxt = stem_tile_advance(q, cur, stride);
+            stem_fetch(q, nxt, tid_l, raw);                         // in flight under the MFMAs and the conv tile's epilogue
+        }
+        const int n = cur.n, py0 = cur.ty * PT, px0 = cur.tx * PT;
+        const int cy0 = 2 * py0 - 1, cx0 = 2 * px0 - 1;      // first conv pixel of the 16x16 tile
+        f32x4_t acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        {
+            const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(smem + buf * kTileBytes);
+            auto read_x = [&](int s, uint4 (&xf)[4]) {
+                int idx = s * 4 + fq_l;
+                idx = idx < 21 ? idx : 20;                   // padded rows carry zero weights; keep the address inside the tile
+                const int c = idx / 7, kh = idx - c * 7;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int ty = wave * 4 + i;
+                    const int e = (c * TH + ty * 2 + kh) * (TW / 2) + fr_l;        // 32-bit word index
+                    xf[i] = make_uint4(tile32[e], tile32[e + 1], tile32[e + 2], tile32[e + 3]);
+                }
+            };
+            // the B fragments one k-step ahead, and no further: with the 96 weight registers there is room for two sets, not six
+            uint4 xa[4], xb[4];
+            read_x(0, xa);
+#pragma unroll
+            for (int s = 0; s < 6; ++s) {
+                uint4 (&xf)[4] = (s & 1) ? xb : xa;
+                if (s + 1 < 6) read_x(s + 1, (s & 1) ? xa : xb);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<bf16x8_t*>(&wf[s][j]), *reinterpret_cast<bf16x8_t*>(&xf[i]),
+                                                                             acc[i][j], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
-    }
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int fr = lane & 15, fq = lane >> 4;
-    f32x4_t acc[4][4];
+        // lane owns conv pixel (row wave*4+i, column fr), channels j*16 + fq*4 .. +3.  (The conv tile is free: the barrier that ended the
+        // previous iteration came after its pooling.)
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    {
-        const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(tile);
-        const uint4* wl16 = reinterpret_cast<const uint4*>(wl);
-#pragma unroll
-        for (int s = 0; s < 6; ++s) {
-            int idx = s * 4 + fq;
-            idx = idx < 21 ? idx : 20;                       // padded rows carry zero weights; keep the address inside the tile
-            const int c = idx / 7, kh = idx - c * 7;
-            uint4 xf[4], wf[4];
+        for (int j = 0; j < 4; ++j) {
+            const int ch = j * 16 + fq_l * 4;
+            const float4 sc = *reinterpret_cast<const float4*>(bn + ch), sh = *reinterpret_cast<const float4*>(bn + 64 + ch);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int ty = wave * 4 + i;
-                const int e = ((c * TH + ty * 2 + kh) * TW + fr * 2) >> 1;
-                xf[i] = make_uint4(tile32[e], tile32[e + 1], tile32[e + 2], tile32[e + 3]);
+                const int ry = wave * 4 + i, cy = cy0 + ry, cx = cx0 + fr_l;
+                uint2 o;
+                if (cy >= 0 && cy < p.Hc && cx >= 0 && cx < p.Wc) {
+                    o.x = pack2_bf16(fmaxf(acc[i][j][0] * sc.x + sh.x, 0.f), fmaxf(acc[i][j][1] * sc.y + sh.y, 0.f));
+                    o.y = pack2_bf16(fmaxf(acc[i][j][2] * sc.z + sh.z, 0.f), fmaxf(acc[i][j][3] * sc.w + sh.w, 0.f));
+                } else {
+                    o.x = o.y = 0xff80ff80u;                 // -inf, -inf
+                }
+                *reinterpret_cast<uint2*>(ct + (ry * 16 + fr_l) * CS + ch * 2) = o;
             }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) wf[j] = wl16[((j * 16 + fr) * WK + (s * 4 + fq) * 8) >> 3];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<bf16x8_t*>(&wf[j]), *reinterpret_cast<bf16x8_t*>(&xf[i]),
-                                                                         acc[i][j], 0, 0, 0);
         }
-    }
-    __syncthreads();                                        // everyone is done with wl / tile: the conv tile takes their place
-    // lane owns conv pixel (row wave*4+i, column fr), channels j*16 + fq*4 .. +3
+        // the next tile's image into the other buffer (last read by the MFMAs of the previous iteration, two barriers ago)
+        if (more) stem_convert(q, nxt, tid_l, raw, reinterpret_cast<bf16_t*>(smem + (buf ^ 1) * kTileBytes));
+        __syncthreads();
+        typedef short s16x8_t __attribute__((ext_vector_type(8)));
+        for (int item = tid_l; item < PT * PT * 8; item += 256) {
+            const int chunk = item & 7, pp = item >> 3;
+            const int pi = pp / PT, pj = pp - pi * PT;
+            const int py = py0 + pi, px = px0 + pj;
+            if (py >= q.Hp || px >= q.Wp) continue;
+            // ReLU outputs are >= 0 and the padding is -inf: as signed 16-bit integers bf16 patterns order like the values
+            s16x8_t m = *reinterpret_cast<const s16x8_t*>(ct + ((2 * pi) * 16 + 2 * pj) * CS + chunk * 16);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int ch = j * 16 + fq * 4;
-        const float4 sc = *reinterpret_cast<const float4*>(p.scale + ch), sh = *reinterpret_cast<const float4*>(p.shift + ch);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int ry = wave * 4 + i, cy = cy0 + ry, cx = cx0 + fr;
-            uint2 o;
-            if (cy >= 0 && cy < p.Hc && cx >= 0 && cx < p.Wc) {
-                o.x = pack2_bf16(fmaxf(acc[i][j][0] * sc.x + sh.x, 0.f), fmaxf(acc[i][j][1] * sc.y + sh.y, 0.f));
-                o.y = pack2_bf16(fmaxf(acc[i][j][2] * sc.z + sh.z, 0.f), fmaxf(acc[i][j][3] * sc.w + sh.w, 0.f));
-            } else {
-                o.x = o.y = 0xff80ff80u;                     // -inf, -inf
+            for (int d = 1; d < 9; ++d) {
+                const s16x8_t v = *reinterpret_cast<const s16x8_t*>(ct + ((2 * pi + d / 3) * 16 + 2 * pj + d % 3) * CS + chunk * 16);
+                m = __builtin_elementwise_max(m, v);
             }
-            *reinterpret_cast<uint2*>(smem + (ry * 16 + fr) * CS + ch * 2) = o;
+            *reinterpret_cast<s16x8_t*>(q.yp + (((long)n * q.Hp + py) * q.Wp + px) * 64 + chunk * 8) = m;
         }
-    }
-    __syncthreads();
-    typedef short s16x8_t __attribute__((ext_vector_type(8)));
-    for (int item = threadIdx.x; item < PT * PT * 8; item += 256) {
-        const int chunk = item & 7, pp = item >> 3;
-        const int pi = pp / PT, pj = pp - pi * PT;
-        const int py = py0 + pi, px = px0 + pj;
-        if (py >= q.Hp || px >= q.Wp) continue;
-        // ReLU outputs are >= 0 and the padding is -inf: as signed 16-bit integers bf16 patterns order like the values
-        s16x8_t m = *reinterpret_cast<const s16x8_t*>(smem + ((2 * pi) * 16 + 2 * pj) * CS + chunk * 16);
-#pragma unroll
-        for (int d = 1; d < 9; ++d) {
-            const s16x8_t v = *reinterpret_cast<const s16x8_t*>(smem + ((2 * pi + d / 3) * 16 + 2 * pj + d % 3) * CS + chunk * 16);
-            m = __builtin_elementwise_max(m, v);
-        }
-        *reinterpret_cast<s16x8_t*>(q.yp + (((long)n * q.Hp + py) * q.Wp + px) * 64 + chunk * 8) = m;
+        __syncthreads();                                     // pooled: the conv tile may be overwritten; the next image tile is visible
+        cur = nxt;
     }
 }
 
@@ -661,9 +758,21 @@ extern "C" int aldi_stem_pool_forward(const aldi_stem_args* a, const void* w_pac
     for (int c = 0; c < 3; ++c) { d.mean[c] = a->mean[c]; d.inv_std[c] = 1.0f / a->std[c]; }
     q.wpk = static_cast<const bf16_t*>(w_packed);
     q.yp = static_cast<bf16_t*>(y_pool);
+    if ((a->Ws & 3) || (reinterpret_cast<uintptr_t>(a->img) & 3))
+        return aldi_set_error_msg(ALDI_ERR_ARG, "stem_pool_forward: the staging rows must be 4-byte aligned (Ws % 4 == 0)");
     q.Hp = (a->Hc - 1) / 2 + 1; q.Wp = (a->Wc - 1) / 2 + 1;
-    dim3 grid(cdiv(q.Wp, 7), cdiv(q.Hp, 7), a->N);
-    hipLaunchKernelGGL(stem_pool_mfma_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), q);
+    q.tiles_x = cdiv(q.Wp, kStemPoolPT); q.tiles_y = cdiv(q.Hp, kStemPoolPT); q.n_tiles = q.tiles_x * q.tiles_y * a->N;
+    // persistent grid: two workgroups per compute unit (what the LDS and the registers allow), a whole number per XCD; never more than tiles
+    static int n_cu = 0;
+    if (!n_cu) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1)
+            return aldi_set_error_msg(ALDI_ERR_HIP, "stem_pool_forward: cannot read the compute-unit count");
+        n_cu = v;
+    }
+    int wgs = aldi_tuning().stem_pool_wgs > 0 ? aldi_tuning().stem_pool_wgs : 2 * n_cu;
+    if (wgs > q.n_tiles) wgs = q.n_tiles;
+    hipLaunchKernelGGL(stem_pool_mfma_kernel, dim3(wgs), dim3(256), 0, static_cast<hipStream_t>(stream), q);
     ALDI_CHECK_LAUNCH();
     return ALDI_OK;
 }

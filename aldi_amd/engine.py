@@ -408,6 +408,7 @@ class RCNN:
         self.mask_bits_inner = os.environ.get("ALDI_MASK_BITS_INNER", "1") == "1"        # ... and of the two inner maps of every bottleneck
         self.level_groups = os.environ.get("ALDI_LEVEL_GROUPS", "1") == "1"              # one launch for a layer applied to several pyramid levels
         self.fused_res2 = os.environ.get("ALDI_FUSED_RES2", "1") == "1"                  # bf16: a res2 bottleneck (no saved activations) in one kernel
+        self.fused_res2_shortcut = os.environ.get("ALDI_FUSED_RES2_SHORTCUT", "1") == "1"  # ... and res2.0's shortcut conv inside that kernel
         self._wg_queue: list = []
         self.sparse_rpn_backward = os.environ.get("ALDI_RPN_SPARSE_BWD", "1") == "1"      # tests flip the attribute to compare with the dense form
         spec = getattr(weights.layout, "img_da", None)
@@ -611,11 +612,16 @@ class RCNN:
                 continue
             for b in range(nb):
                 p = f"{bu}res{si + 2}.{b}."
-                sc = (yield x, p + "shortcut", {}) if b == 0 else x
                 if si == 0 and fuse2:
+                    # res2.0's projection shortcut is formed inside the block's kernel from the x tile it already holds (no launch, no 256-channel
+                    # map through memory); res = x there: not read
+                    fold_sc = b == 0 and self.fused_res2_shortcut
+                    sc = (yield x, p + "shortcut", {}) if b == 0 and not fold_sc else x
                     x = ops.bottleneck_fused(x, sc, fw[p + "conv1"], fw[p + "conv2"], fw[p + "conv3"], W.shift(p + "conv1"), W.shift(p + "conv2"),
-                                             W.shift(p + "conv3"), out=prefix_out if (prefix_out is not None and b == nb - 1) else None)
+                                             W.shift(p + "conv3"), out=prefix_out if (prefix_out is not None and b == nb - 1) else None,
+                                             shortcut=(W.w(p + "shortcut"), W.scale(p + "shortcut"), W.shift(p + "shortcut")) if fold_sc else None)
                     continue
+                sc = (yield x, p + "shortcut", {}) if b == 0 else x
                 # every saved ReLU output's mask as BITS beside it (1/16 of the tensor): what the data-gradient launch that needs the mask -- the
                 # next block's conv1 / the lateral conv for a block output, conv3's / conv2's for the two inner maps -- multiplies by instead of
                 # reading the whole activation again for its sign; with bits those launches also take the direct epilogue (csrc/igemm.hip)

@@ -293,15 +293,26 @@ class FoldWeightsPlan:
         L.call("aldi_fold_weights_batch", _p(self.items), self.n, self.total_chunks, stream_ptr())
 
 
-def bottleneck_fused(x: torch.Tensor, res: torch.Tensor, w1, w2, w3, b1, b2, b3, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def bottleneck_fused(x: torch.Tensor, res: torch.Tensor, w1, w2, w3, b1, b2, b3, out: Optional[torch.Tensor] = None, *,
+                     shortcut=None) -> torch.Tensor:
     """one ResNet bottleneck without saved activations in one kernel (aldi_bottleneck_fused): x [N,H,W,Cin] bf16, res [N,H,W,Cout]
-    (x itself for an identity block), folded bf16 weights w1 [mid,1,1,Cin], w2 [mid,3,3,mid], w3 [Cout,1,1,mid], fp32 shifts"""
+    (x itself for an identity block), folded bf16 weights w1 [mid,1,1,Cin], w2 [mid,3,3,mid], w3 [Cout,1,1,mid], fp32 shifts.
+    shortcut = (w [Cout,1,1,Cin] bf16 unfolded, scale, shift): the stage's first block forms its residual, the projection shortcut of x,
+    inside the kernel (aldi_bottleneck_fused_sc: bit for bit conv2d(x, w, scale, shift) as the residual); pass res = x, it is not read."""
     N, H, W_, Cin = x.shape
     mid, Cout = w1.shape[0], w3.shape[0]
-    assert x.dtype == torch.bfloat16 and x.is_contiguous() and res.is_contiguous() and res.shape == (N, H, W_, Cout), (x.shape, res.shape)
+    assert x.dtype == torch.bfloat16 and x.is_contiguous()
     assert w1.numel() == mid * Cin and w2.numel() == mid * 9 * mid and w3.numel() == Cout * mid and w1.dtype == torch.bfloat16
     if out is None:
         out = torch.empty((N, H, W_, Cout), dtype=x.dtype, device=x.device)
+    if shortcut is not None:
+        wsc, ssc, bsc = shortcut
+        assert wsc.dtype == torch.bfloat16 and wsc.is_contiguous() and wsc.numel() == Cout * Cin, wsc.shape
+        assert ssc.dtype == bsc.dtype == torch.float32 and ssc.numel() == bsc.numel() == Cout
+        a = L.BottleneckArgs(_p(x), None, _p(out), _p(w1), _p(w2), _p(w3), _p(b1), _p(b2), _p(b3), N, H, W_, Cin, mid, Cout)
+        L.call("aldi_bottleneck_fused_sc", C.byref(a), _p(wsc), _p(ssc), _p(bsc), stream_ptr())
+        return out
+    assert res.is_contiguous() and res.shape == (N, H, W_, Cout), (x.shape, res.shape)
     a = L.BottleneckArgs(_p(x), _p(res), _p(out), _p(w1), _p(w2), _p(w3), _p(b1), _p(b2), _p(b3), N, H, W_, Cin, mid, Cout)
     L.call("aldi_bottleneck_fused", C.byref(a), stream_ptr())
     return out

@@ -103,6 +103,7 @@ int aldi_noop(aldi_stream_t stream);
  *   msda_gather_list     walk form: list length the tile sizes aim at (1500)
  *   colsum_blocks, colsum_minrows, colsum_nt, colsum_block_kb   aldi_bias_grad launch geometry
  *   stem_mfma            1 = MFMA stem kernel in bf16 mode
+ *   stem_pool_wgs        workgroups of the persistent stem + pool kernel (0 = two per compute unit, the default; never more than tiles)
  *   sab_blocks, ln_bwd_blocks, ln_bwd_blocks_narrow   ConvNeXt scale-and-bias / LayerNorm backward launch geometry
  * aldi_last_dispatch(): name of the kernel variant chosen by the most recent aldi_conv_igemm / aldi_conv_wgrad call on
  * this thread, e.g. "igemm<bf16,256,128,4,2,flat,halo>" or "wgrad_bf16_big splits=4" (valid until the next call). */
@@ -241,6 +242,11 @@ typedef struct aldi_bottleneck_args {
     int N, H, W, Cin, mid, Cout;
 } aldi_bottleneck_args;
 int aldi_bottleneck_fused(const aldi_bottleneck_args* a, aldi_stream_t stream);
+/* The FIRST block of res2 with its projection shortcut inside the kernel: res = bf16( (wsc . x) * sc_scale + sc_shift ) is formed from
+ * the tile's own x pixels in phase 3 (two MFMA k-steps of 32 channels in ascending order, one rounding: bit for bit what
+ * aldi_conv_igemm stores for that 1x1 conv) instead of being written to and read back from memory by a launch of its own.
+ * `a->res` is ignored; wsc [Cout][Cin] bf16 WITHOUT the scale folded, sc_scale / sc_shift [Cout] fp32.  Cin = 64 only. */
+int aldi_bottleneck_fused_sc(const aldi_bottleneck_args* a, const void* wsc, const float* sc_scale, const float* sc_shift, aldi_stream_t stream);
 /* out[r][c] = bf16(w[r][c] * scale[r]) for a DEVICE table of fp32 matrices (rows * cols a multiple of 8, 16-byte aligned);
  * matrix i owns the 8-element chunks [chunk_begin_i, chunk_begin_{i+1}) of the launch. */
 typedef struct aldi_fold_item {
