@@ -100,6 +100,14 @@ def plan_dispatch(args, n: int = 1) -> str:
     return buf.value.decode()
 
 
+def plan_pair_dispatch(args, pre) -> str:
+    """aldi_conv_pair_igemm_plan: the kernel aldi_conv_pair_igemm would run for (ConvArgs, ConvPreArgs) -- raises AldiHipError with the reason
+    when the combination is not one the pair kernel takes; nothing is launched"""
+    buf = C.create_string_buffer(224)
+    call("aldi_conv_pair_igemm_plan", C.byref(args), C.byref(pre), buf, len(buf))
+    return buf.value.decode()
+
+
 def plan_wgrad_dispatch(args, n: int = 1, group: bool = False):
     """aldi_conv_wgrad_plan: -> (name, workspace bytes) of aldi_conv_wgrad (args a WgradArgs or an array; group False) / aldi_conv_wgrad_group
     (an array of n; group True) under the current knobs -- nothing is launched, no GPU is needed and no pointer is dereferenced"""
@@ -126,6 +134,12 @@ class ConvArgs(C.Structure):
         ("relu", c_int), ("res_mode", c_int), ("out_scale", c_int), ("OH", c_int), ("OW", c_int),
         ("dtype", c_int), ("ws", c_void_p), ("ksplit", c_int), ("mask_bits", c_void_p), ("bits_out", c_void_p),
     ]
+
+
+class ConvPreArgs(C.Structure):
+    """aldi_conv_pre_args (include/aldi_hip.h)"""
+    _fields_ = [("x2", c_void_p), ("w2", c_void_p), ("scale2", c_void_p), ("shift2", c_void_p),
+                ("H2", c_int), ("W2", c_int), ("Cin2", c_int), ("stride2", c_int), ("rounding", c_int)]
 
 
 class WgradArgs(C.Structure):

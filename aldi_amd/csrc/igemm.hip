@@ -84,7 +84,8 @@ __device__ __forceinline__ void igemm_epilogue(const ConvDev& p, f32x4_t (&acc)[
             const int rowl0 = tid / CPR, ch8 = tid % CPR;
             const int c = n0 + ch8 * 8;
             if (c >= p.Cout) return;
-            const bool plain = p.out_scale == 1 && p.res_mode != 2;
+            const bool plain = p.out_scale == 1 && p.res_mode < 2;
+            const int up = p.res_mode & 1;          // res_mode 3: the residual's grid is the CEIL-halved one, and only even (ho, wo) have a residual pixel
             const unsigned char* rd = stg + rowl0 * ROWB + ch8 * 16;
             typedef short s16x2_t __attribute__((ext_vector_type(2)));
             // Branch-free and latency-flat: byte offsets (out-of-tile rows -> the dropped/zero-filled range), then ALL the
@@ -99,6 +100,7 @@ __device__ __forceinline__ void igemm_epilogue(const ConvDev& p, f32x4_t (&acc)[
                 const int m = m0 + rowl0 + it * RPI;
                 const bool ok = m < p.M;
                 unsigned oidx, ridx;
+                bool rok = ok;
                 if (plain) {
                     oidx = (unsigned)m * (unsigned)p.Cout;
                     ridx = oidx;
@@ -109,11 +111,13 @@ __device__ __forceinline__ void igemm_epilogue(const ConvDev& p, f32x4_t (&acc)[
                     const int ho = r / p.Wo, wo = r - ho * p.Wo;
                     if (p.out_scale == 1) oidx = (unsigned)mm * (unsigned)p.Cout;
                     else oidx = (unsigned)((((long)n * p.OH + ho * p.out_scale) * p.OW + wo * p.out_scale) * p.Cout);
-                    if (p.res_mode == 2) ridx = (unsigned)((((long)n * (p.Ho >> 1) + (ho >> 1)) * (p.Wo >> 1) + (wo >> 1)) * p.Cout);
-                    else ridx = oidx;
+                    if (p.res_mode >= 2) {
+                        ridx = (unsigned)((((long)n * ((p.Ho + up) >> 1) + (ho >> 1)) * ((p.Wo + up) >> 1) + (wo >> 1)) * p.Cout);
+                        rok = ok && !(up & (ho | wo));          // (odd pixels: the out-of-range offset, zeros -- + 0.0 as with a zero-stuffed map)
+                    } else ridx = oidx;
                 }
                 ooff[it] = ok ? (oidx + (unsigned)c) * 2u : OOBX;
-                roff[it] = ok ? (ridx + (unsigned)c) * 2u : OOBX;
+                roff[it] = rok ? (ridx + (unsigned)c) * 2u : OOBX;
                 boff[it] = ok ? (oidx + (unsigned)c) >> 3 : OOBX;          // this lane's 8 channels = one byte of a bit mask
             }
             u32x4_t rres[NI], rmsk[NI];
@@ -199,7 +203,8 @@ __device__ __forceinline__ void igemm_epilogue(const ConvDev& p, f32x4_t (&acc)[
         int m = m0 + wm * (BM / WM) + i * 16 + fr;
         if (m >= p.M) continue;
         long oidx, ridx = 0;
-        if (p.out_scale == 1 && p.res_mode != 2) {
+        bool rok = true;
+        if (p.out_scale == 1 && p.res_mode < 2) {
             oidx = (long)m * p.Cout;
             ridx = oidx;
         } else {
@@ -208,8 +213,11 @@ __device__ __forceinline__ void igemm_epilogue(const ConvDev& p, f32x4_t (&acc)[
             int ho = r / p.Wo, wo = r - ho * p.Wo;
             if (p.out_scale == 1) oidx = (long)m * p.Cout;
             else oidx = (((long)n * p.OH + ho * p.out_scale) * p.OW + wo * p.out_scale) * p.Cout;
-            if (p.res_mode == 2) ridx = (((long)n * (p.Ho >> 1) + (ho >> 1)) * (p.Wo >> 1) + (wo >> 1)) * p.Cout;
-            else ridx = oidx;
+            const int up = p.res_mode & 1;          // res_mode 3: ceil-halved residual grid, even (ho, wo) only
+            if (p.res_mode >= 2) {
+                ridx = (((long)n * ((p.Ho + up) >> 1) + (ho >> 1)) * ((p.Wo + up) >> 1) + (wo >> 1)) * p.Cout;
+                rok = !(up & (ho | wo));
+            } else ridx = oidx;
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -225,8 +233,8 @@ __device__ __forceinline__ void igemm_epilogue(const ConvDev& p, f32x4_t (&acc)[
                 v[0] += sh.x; v[1] += sh.y; v[2] += sh.z; v[3] += sh.w;
             }
             if (p.res_mode) {
-                float r4[4];
-                load4(R + ridx + c, r4);
+                float r4[4] = {0.f, 0.f, 0.f, 0.f};
+                if (rok) load4(R + ridx + c, r4);
                 v[0] += r4[0]; v[1] += r4[1]; v[2] += r4[2]; v[3] += r4[3];
             }
             if (p.relu) {
@@ -278,7 +286,8 @@ __device__ __forceinline__ unsigned lds_read_u8(unsigned addr) {
     asm volatile("ds_read_u8 %0, %1" : "=v"(v) : "v"(addr));
     return v;
 }
-template <int BM, int BN, int WM, int WN, bool RESL>
+// TWO (the pair form, igemm_pair.h): conv * scale + shift is rounded to bf16 BEFORE the residual is added, as the staged epilogue does -- two roundings
+template <int BM, int BN, int WM, int WN, bool RESL, bool TWO = false>
 __device__ __forceinline__ void igemm_epilogue_direct(const ConvDev& p, f32x4_t (&acc)[BM / WM / 16][BN / WN / 16], const int m0, const int n0,
                                                       u32x4_t (&rres)[BM / WM / 16][BN / WN / 32], const unsigned aux_addr) {
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16, WNE = BN / WN, H = WNE / 32;
@@ -345,6 +354,16 @@ __device__ __forceinline__ void igemm_epilogue_direct(const ConvDev& p, f32x4_t 
             if (has_sh) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { v[e] += __uint_as_float(sh[2 * h][e]); v[4 + e] += __uint_as_float(sh[2 * h + 1][e]); }
+            }
+            if constexpr (RESL && TWO) {
+                if (has_res) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const unsigned r2 = pack2_bf16(v[2 * q], v[2 * q + 1]);
+                        v[2 * q] = __uint_as_float(r2 << 16);
+                        v[2 * q + 1] = __uint_as_float(r2 & 0xffff0000u);
+                    }
+                }
             }
             if constexpr (RESL) {
                 if (has_res) {                  // fp32 add before the single rounding
@@ -456,15 +475,17 @@ __device__ __forceinline__ void igemm_body(const ConvDev& p, int bid, const int 
                 for (int i = 0; i < BM / WM / 16; ++i) {
                     const int m = m0 + wm * (BM / WM) + i * 16 + (lane & 15);
                     unsigned ridx = (unsigned)m;
-                    if (p.res_mode == 2) {                      // FPN top-down: the coarser map's pixel (ho >> 1, wo >> 1)
-                        const int mm = m < p.M ? m : 0;
+                    bool rok = true;
+                    if (p.res_mode >= 2) {                      // FPN top-down: the coarser map's pixel (ho >> 1, wo >> 1); 3: a stride-2 map's pixel, even (ho, wo) only
+                        const int mm = m < p.M ? m : 0, up = p.res_mode & 1;
                         const int n = mm / (p.Ho * p.Wo), r = mm - n * (p.Ho * p.Wo), ho = r / p.Wo, wo = r - ho * p.Wo;
-                        ridx = (unsigned)((n * (p.Ho >> 1) + (ho >> 1)) * (p.Wo >> 1) + (wo >> 1));
+                        ridx = (unsigned)((n * ((p.Ho + up) >> 1) + (ho >> 1)) * ((p.Wo + up) >> 1) + (wo >> 1));
+                        rok = !(up & (ho | wo));
                     }
 #pragma unroll
                     for (int h = 0; h < BN / WN / 32; ++h) {
                         const int ch = n0 + wn * (BN / WN) + h * 32 + (lane >> 4) * 8;
-                        const bool ok = p.res_mode && m < p.M && ch < p.Cout;
+                        const bool ok = p.res_mode && rok && m < p.M && ch < p.Cout;
                         rres[i][h] = __builtin_amdgcn_raw_buffer_load_b128(rr, ok ? (ridx * (unsigned)p.Cout + (unsigned)ch) * 2u : OOB, 0, 0);
                     }
                 }
@@ -1041,6 +1062,7 @@ __global__ __launch_bounds__(512) void igemm_halo_rs_kernel(ConvDev p) {
 
 #include "igemm_halo64.h"
 #include "igemm_ws.h"
+#include "igemm_pair.h"
 
 // (the 240-pixel halo tile is sized for TWO workgroups per CU: 6 waves each = 3 waves per SIMD, 80 KB of LDS each)
 template <int BM, int NT, bool HALO> constexpr int min_waves_per_simd() { return HALO && BM == 240 ? 2 * NT / 256 : 1; }
@@ -1203,6 +1225,19 @@ int conv_one(const aldi_conv_args* a, const bool dry, hipStream_t st, char* name
     return ALDI_OK;
 }
 
+// the pair form: plan (igemm_select.h), and unless `dry` launch
+int conv_pair(const aldi_conv_args* a, const aldi_conv_pre_args* pre, const bool dry, hipStream_t st, char* name) {
+    ConvDev d;
+    PairPre q;
+    bool two = false;
+    if (int rc = plan_conv_pair(a, pre, aldi_tuning(), d, q, two)) return rc;
+    pair_dispatch_name(two, name, kNameCap);
+    if (dry) return ALDI_OK;
+    if (int rc = launch_pair(two, d, q, st)) return rc;
+    aldi_note_dispatch(name);
+    return ALDI_OK;
+}
+
 // n convolutions: one launch when they are one layer shape, else n single ones (name: the last one's)
 int conv_many(const aldi_conv_args* args, const int n, const bool dry, hipStream_t st, char* name) {
     if (!args || n < 1) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm_group: no problems");
@@ -1231,6 +1266,18 @@ extern "C" int aldi_conv_igemm(const aldi_conv_args* a, aldi_stream_t stream) {
 extern "C" int aldi_conv_igemm_group(const aldi_conv_args* args, int n, aldi_stream_t stream) {
     char name[kNameCap];
     return conv_many(args, n, false, static_cast<hipStream_t>(stream), name);
+}
+
+extern "C" int aldi_conv_pair_igemm(const aldi_conv_args* a, const aldi_conv_pre_args* pre, aldi_stream_t stream) {
+    char name[kNameCap];
+    return conv_pair(a, pre, false, static_cast<hipStream_t>(stream), name);
+}
+
+extern "C" int aldi_conv_pair_igemm_plan(const aldi_conv_args* a, const aldi_conv_pre_args* pre, char* name, int cap) {
+    char buf[kNameCap] = "";
+    const int rc = conv_pair(a, pre, true, nullptr, buf);
+    if (rc == ALDI_OK && name && cap > 0) snprintf(name, (size_t)cap, "%s", buf);
+    return rc;
 }
 
 extern "C" int aldi_conv_igemm_plan(const aldi_conv_args* args, int n, char* name, int cap) {

@@ -299,6 +299,7 @@ inline int fill_convdev(const aldi_conv_args* a, ConvDev& d) {
         return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: Cin must be a multiple of 32 (bf16) / 16 (f32) for KxK convs; of a 16-B chunk for 1x1");
     if (a->Cout % 4 != 0) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: Cout must be a multiple of 4");
     if (a->res_mode == 2 && ((a->Ho & 1) || (a->Wo & 1))) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: upsample residual needs even Ho,Wo");
+    if (a->res_mode < 0 || a->res_mode > 3 || (a->res_mode == 3 && a->out_scale > 1)) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: res_mode is 0 .. 3 (3: dense output only)");
     if (a->res_mode && !a->res) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_igemm: res_mode set without res");
     d.x = a->x; d.w = a->w; d.y = a->y; d.y_f32 = a->y_f32; d.scale = a->scale; d.shift = a->shift;
     d.res = a->res; d.mask = a->mask;
@@ -376,5 +377,38 @@ inline int plan_conv_group(const aldi_conv_args* args, int n, const AldiTuning& 
     d.xcd = tn.igemm_xcd; d.dbg = tn.igemm_dbg;
     return ALDI_OK;
 }
+
+// ---- the pair form (igemm_pair.h): a 1x1 conv whose residual is a second 1x1 conv, formed in the same workgroup
+struct PairPre {
+    const void* x2; const void* w2; const float* scale2; const float* shift2;
+    int H2, W2, Cin2, stride2;
+    unsigned x2_bytes, w2_bytes;
+};
+// what igemm_pair_kernel takes: d = the main conv (fill_convdev), q = the inner one
+inline bool pair_ok(const ConvDev& d, const bool f32, const PairPre& q) {
+    return !f32 && plain_1x1(d) && d.y && !d.y_f32 && d.out_scale == 1 && !d.res_mode && !d.mask && !d.mask_bits && d.ksplit <= 1 && d.Cout % 64 == 0 &&
+           d.K % 32 == 0 && q.x2 && q.w2 && q.Cin2 > 0 && q.Cin2 % 32 == 0 && q.stride2 >= 1 && q.H2 >= 1 && q.W2 >= 1 &&
+           (q.H2 - 1) / q.stride2 + 1 == d.Ho && (q.W2 - 1) / q.stride2 + 1 == d.Wo;
+}
+// d: the main conv as the kernel takes it (res_mode = 1: its epilogue adds the inner conv's rounded result); two: the outer sum is rounded twice
+inline int plan_conv_pair(const aldi_conv_args* a, const aldi_conv_pre_args* pre, const AldiTuning& tn, ConvDev& d, PairPre& q, bool& two) {
+    if (!pre) return aldi_set_error_msg(ALDI_ERR_ARG, "conv_pair_igemm: null pointer");
+    if (int rc = fill_convdev(a, d)) return rc;
+    q = PairPre{pre->x2, pre->w2, pre->scale2, pre->shift2, pre->H2, pre->W2, pre->Cin2, pre->stride2, 0u, 0u};
+    const size_t xb = (size_t)(a->N > 0 ? a->N : 0) * (size_t)(q.H2 > 0 ? q.H2 : 0) * (size_t)(q.W2 > 0 ? q.W2 : 0) * (size_t)(q.Cin2 > 0 ? q.Cin2 : 0) * 2;
+    const size_t wb = (size_t)a->Cout * (size_t)(q.Cin2 > 0 ? q.Cin2 : 0) * 2;
+    if (a->dtype != ALDI_BF16 || a->ksplit > 1 || !pair_ok(d, false, q) || xb >= 0x80000000ull || wb >= 0x80000000ull || (unsigned)pre->rounding > 2u)
+        return aldi_set_error_msg(ALDI_ERR_ARG, "conv_pair_igemm: takes bf16, two 1x1 convs without padding on one output grid, the main one plain (stride 1, no res / "
+                                                "mask / fp32 output / scatter / split-K), Cout % 64 == 0, Cin % 32 == 0, Cin2 % 32 == 0");
+    q.x2_bytes = (unsigned)xb; q.w2_bytes = (unsigned)wb;
+    d.res_mode = 1;                 // what the UNFUSED main launch is: the same conv with the inner one's map as `res`
+    d.res = pre->x2;                // (never read: only "not null" matters to the selection)
+    two = pre->rounding == 2;
+    if (pre->rounding == 0) two = kTiles[select_tile(d, tn, false, 0).tile].epi == 0;
+    d.res = nullptr;
+    d.xcd = tn.igemm_xcd; d.dbg = tn.igemm_dbg;
+    return ALDI_OK;
+}
+inline int pair_dispatch_name(const bool two, char* name, int cap) { return snprintf(name, cap, "igemm_pair<bf16,128,64,4,1,pipe,tap,round%d>", two ? 2 : 1); }
 
 }  // namespace

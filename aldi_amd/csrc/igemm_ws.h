@@ -57,8 +57,10 @@ __global__ __launch_bounds__(256, 2) void igemm_ws_kernel(ConvDev p, const int n
     }
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(static_cast<const T*>(p.x)), 0, p.x_bytes, 0x00020000);
     const unsigned out_bytes = (unsigned)p.M * (unsigned)p.Cout * 2u;
-    const bool res_up = p.res_mode == 2;                      // the residual is the coarser pyramid level's map, nearest-upsampled (FPN top-down sum): [N][Ho / 2][Wo / 2][Cout]
-    const __amdgpu_buffer_rsrc_t rr = make_rsrc_uniform(p.res, res_up ? out_bytes >> 2 : out_bytes);
+    const bool res_up = p.res_mode >= 2;                      // the residual is the coarser pyramid level's map, nearest-upsampled (FPN top-down sum): [N][Ho / 2][Wo / 2][Cout]
+    const unsigned res_s2 = (unsigned)p.res_mode & 1u;        // ... or (3) a stride-2 map [N][(Ho + 1) / 2][(Wo + 1) / 2][Cout] added at even (ho, wo) only: + 0.0 elsewhere
+    const unsigned rHo = (unsigned)(p.Ho + (int)res_s2) >> 1, rWo = (unsigned)(p.Wo + (int)res_s2) >> 1;
+    const __amdgpu_buffer_rsrc_t rr = make_rsrc_uniform(p.res, res_up ? (unsigned)p.N * rHo * rWo * (unsigned)p.Cout * 2u : out_bytes);
     const __amdgpu_buffer_rsrc_t rmb = make_rsrc_uniform(p.mask_bits, out_bytes >> 4);
     const __amdgpu_buffer_rsrc_t ry = make_rsrc_uniform(p.y, out_bytes);
     const __amdgpu_buffer_rsrc_t rbo = make_rsrc_uniform(p.bits_out, out_bytes >> 4);
@@ -107,11 +109,13 @@ __global__ __launch_bounds__(256, 2) void igemm_ws_kernel(ConvDev p, const int n
                 const unsigned m = (unsigned)(m0 + i * 16 + fr), c = (unsigned)(n0 + h * 32 + fq * 8);
                 if (has_res) {
                     unsigned row = m;
+                    bool rok = m < (unsigned)p.M;
                     if (res_up) {
                         const unsigned t_ = fdiv(m, (unsigned)p.Wo, inv_wo), wo = m - t_ * (unsigned)p.Wo, n = fdiv(t_, (unsigned)p.Ho, inv_ho), ho = t_ - n * (unsigned)p.Ho;
-                        row = (n * (unsigned)(p.Ho >> 1) + (ho >> 1)) * (unsigned)(p.Wo >> 1) + (wo >> 1);
+                        row = (n * rHo + (ho >> 1)) * rWo + (wo >> 1);
+                        rok = rok && !(res_s2 & (ho | wo));
                     }
-                    rres[i][h] = __builtin_amdgcn_raw_buffer_load_b128(rr, m < (unsigned)p.M ? row * C2 + c * 2u : OOB, 0, 0);      // (rows >= M: out of range, zeros)
+                    rres[i][h] = __builtin_amdgcn_raw_buffer_load_b128(rr, rok ? row * C2 + c * 2u : OOB, 0, 0);      // (rows >= M, odd pixels of a stride-2 map: out of range, zeros)
                 }
                 if (has_mb) mb[i][h] = __builtin_amdgcn_raw_buffer_load_b8(rmb, m * C8 + (c >> 3), 0, 0);
             }

@@ -409,6 +409,8 @@ class RCNN:
         self.level_groups = os.environ.get("ALDI_LEVEL_GROUPS", "1") == "1"              # one launch for a layer applied to several pyramid levels
         self.fused_res2 = os.environ.get("ALDI_FUSED_RES2", "1") == "1"                  # bf16: a res2 bottleneck (no saved activations) in one kernel
         self.fused_res2_shortcut = os.environ.get("ALDI_FUSED_RES2_SHORTCUT", "1") == "1"  # ... and res2.0's shortcut conv inside that kernel
+        # bf16: the projection shortcut of res3.0 / res4.0 / res5.0 inside the block's conv3 launch (csrc/igemm_pair.h; same bits)
+        self.fused_stage_entrance = os.environ.get("ALDI_FUSED_STAGE_ENTRANCE", "1") == "1"
         self._wg_queue: list = []
         self.sparse_rpn_backward = os.environ.get("ALDI_RPN_SPARSE_BWD", "1") == "1"      # tests flip the attribute to compare with the dense form
         spec = getattr(weights.layout, "img_da", None)
@@ -484,12 +486,17 @@ class RCNN:
         return t
 
     # ------------------------------------------------------------------ trunk
-    def _conv_call(self, x, name, *, relu=False, res=None, res_mode=0, want_f32=False, out=None, bits_out=None):
-        """(x, weight, conv2d kwargs) of layer `name` applied to x"""
+    def _conv_call(self, x, name, *, relu=False, res=None, res_mode=0, want_f32=False, out=None, bits_out=None, pre=None):
+        """(x, weight, conv2d kwargs) of layer `name` applied to x.  pre = (x2, layer name): the residual is that 1x1 layer applied to x2, formed
+        inside this launch (ops.conv2d's `pre`)"""
         W = self.wts
         p = W.layout.t[name]
-        return x, W.w(name), dict(stride=p.stride, pad=p.pad, scale=W.scale(name), shift=W.shift(name), res=res, res_mode=res_mode, relu=relu,
-                                  want_f32=want_f32, out=out, bits_out=bits_out)
+        kw = dict(stride=p.stride, pad=p.pad, scale=W.scale(name), shift=W.shift(name), res=res, res_mode=res_mode, relu=relu,
+                  want_f32=want_f32, out=out, bits_out=bits_out)
+        if pre is not None:
+            x2, n2 = pre
+            kw["pre"] = (x2, W.w(n2), W.scale(n2), W.shift(n2), W.layout.t[n2].stride)
+        return x, W.w(name), kw
 
     def conv(self, x, name, **kw):
         x, w, kw = self._conv_call(x, name, **kw)
@@ -549,15 +556,17 @@ class RCNN:
                         except StopIteration as e:
                             rb, res[1] = None, e.value
                 continue
-            if ra is not None and rb is not None:
+            paired = any(not isinstance(r, list) and r[2].get("pre") is not None for r in (ra, rb) if r is not None)     # (a pair launch has no group form)
+            if ra is not None and rb is not None and not paired:
                 la, lb = (ra if isinstance(ra, list) else [ra]), (rb if isinstance(rb, list) else [rb])
                 ys = ops.conv2d_group([eng_a._conv_call(r[0], r[1], **r[2]) for r in la] + [eng_b._conv_call(r[0], r[1], **r[2]) for r in lb])
                 ya = ys[:len(la)] if isinstance(ra, list) else ys[0]
                 yb = ys[len(la):] if isinstance(rb, list) else ys[len(la)]
-            elif ra is not None:
-                ya = eng_a._serve(ra)
             else:
-                yb = eng_b._serve(rb)
+                if ra is not None:
+                    ya = eng_a._serve(ra)
+                if rb is not None:
+                    yb = eng_b._serve(rb)
             if ra is not None:
                 try:
                     ra = gen_a.send(ya)
@@ -621,7 +630,9 @@ class RCNN:
                                              W.shift(p + "conv3"), out=prefix_out if (prefix_out is not None and b == nb - 1) else None,
                                              shortcut=(W.w(p + "shortcut"), W.scale(p + "shortcut"), W.shift(p + "shortcut")) if fold_sc else None)
                     continue
-                sc = (yield x, p + "shortcut", {}) if b == 0 else x
+                # a stage's first block: the projection shortcut is formed inside conv3's launch (no launch and no [N][Ho][Wo][4 * mid] map of its own)
+                fold_sc = b == 0 and self.dtype == torch.bfloat16 and self.fused_stage_entrance
+                sc = (yield x, p + "shortcut", {}) if b == 0 and not fold_sc else x
                 # every saved ReLU output's mask as BITS beside it (1/16 of the tensor): what the data-gradient launch that needs the mask -- the
                 # next block's conv1 / the lateral conv for a block output, conv3's / conv2's for the two inner maps -- multiplies by instead of
                 # reading the whole activation again for its sign; with bits those launches also take the direct epilogue (csrc/igemm.hip)
@@ -639,7 +650,10 @@ class RCNN:
                 b2 = bits_for(h1, p + "conv2") if self.mask_bits_inner else None
                 h2 = yield h1, p + "conv2", dict(relu=True, bits_out=b2)
                 bits = bits_for(h2, p + "conv3")
-                out = yield h2, p + "conv3", dict(relu=True, res=sc, res_mode=1, bits_out=bits)
+                if fold_sc:
+                    out = yield h2, p + "conv3", dict(relu=True, bits_out=bits, pre=(x, p + "shortcut"))
+                else:
+                    out = yield h2, p + "conv3", dict(relu=True, res=sc, res_mode=1, bits_out=bits)
                 if save and si > 0:
                     blocks.append((p, x, h1, h2, out, b == 0))
                     if bits is not None:
@@ -1354,7 +1368,7 @@ class RCNN:
         # those maps NOW on the side stream, beside the box head's backward, instead of in the middle of the data-gradient chain
         gx_pre, gx_ev = {}, None
         side0 = self._wgrad_stream()
-        if side0 is not None and "cs" in c:
+        if side0 is not None and "cs" in c and not self._fold_stage_grad():     # (folded: the gradient stays on the compact grid, no zero map)
             side0.wait_stream(torch.cuda.current_stream())     # (fork: inside a graph capture the side stream must descend from the captured one)
             with torch.cuda.stream(side0):
                 for si_, ci_ in ((3, 2), (2, 1)):
@@ -1492,21 +1506,41 @@ class RCNN:
                     self._grads_final(stage_names)
                     if si == 1:
                         break                                           # stage input (res2 output) needs no gradient
-                    stride = W.layout.t[p + "conv1"].stride
-                    Hin, Win = xin.shape[1], xin.shape[2]
                     gx = gx_pre.pop(si, None)
-                    if gx is None or gx.shape != xin.shape:
-                        gx = torch.zeros_like(xin)
-                    else:
+                    if gx is not None and gx.shape == xin.shape:
                         torch.cuda.current_stream().wait_event(gx_ev)
                         gx.record_stream(torch.cuda.current_stream())
-                    ops.conv2d(g, W.wt(p + "shortcut"), out=gx, out_scale=stride, out_hw=(Hin, Win))
-                    ops.conv2d(g1, W.wt(p + "conv1"), out=gx, out_scale=stride, out_hw=(Hin, Win), res=gx, res_mode=1)
-                    lvl = si + 1                                        # this stage's input is C_{lvl}
-                    g = ops.conv2d(gprev[lvl], W.wt(f"backbone.fpn_lateral{lvl}"), res=gx, res_mode=1, **self._relu_mask(c, xin))
+                    else:
+                        gx = None
+                    g = self._stage_input_grad(c, si, p, xin, g, g1, gprev[si + 1], gx)
                 else:
                     g = ops.conv2d(g1, W.wt(p + "conv1"), res=g, res_mode=1, **self._relu_mask(c, xin))
         self._join_wgrads()
+
+    def _fold_stage_grad(self) -> bool:
+        return self.dtype == torch.bfloat16 and self.fused_stage_entrance
+
+    def _stage_input_grad(self, c: Ctx, si: int, p: str, xin: torch.Tensor, g: torch.Tensor, g1: torch.Tensor, gprev: torch.Tensor,
+                          gx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """d(loss)/d(C_{si+1}), the input of stage si (2: res4, 3: res5) whose first block is `p`, masked by the input's ReLU: the shortcut's and
+        conv1's data gradients (of g = d/d(block output) and g1 = d/d(conv1 output); both 1x1 at the stage's stride) + the lateral conv's (of
+        gprev = d/d(the lateral's output)).  gx: a zero map of xin's shape cleared ahead of time (unfolded form only).
+        Folded (bf16, fused_stage_entrance): ONE pair launch forms the first two on the compact output grid of the stride, and the lateral's
+        launch adds that as a zero-stuffed stride-2 residual (res_mode 3) -- no full-size zero map is cleared, scattered into twice and read back.
+        Same bits: the pair rounds twice, as the two scattering launches do (out_scale > 1 takes the staged epilogue)."""
+        W = self.wts
+        stride = W.layout.t[p + "conv1"].stride
+        lvl = si + 1
+        lat = W.wt(f"backbone.fpn_lateral{lvl}")
+        if self._fold_stage_grad() and stride == 2:
+            gq = ops.conv2d(g1, W.wt(p + "conv1"), pre=(g, W.wt(p + "shortcut"), None, None, 1, 2))
+            return ops.conv2d(gprev, lat, res=gq, res_mode=3, **self._relu_mask(c, xin))
+        Hin, Win = xin.shape[1], xin.shape[2]
+        if gx is None:
+            gx = torch.zeros_like(xin)
+        ops.conv2d(g, W.wt(p + "shortcut"), out=gx, out_scale=stride, out_hw=(Hin, Win))
+        ops.conv2d(g1, W.wt(p + "conv1"), out=gx, out_scale=stride, out_hw=(Hin, Win), res=gx, res_mode=1)
+        return ops.conv2d(gprev, lat, res=gx, res_mode=1, **self._relu_mask(c, xin))
 
     def trunk_backward(self, c: Ctx, gC: Dict[int, Optional[torch.Tensor]]):
         """backward of the bare trunk (trunk_steps(..., fpn=False), fp32): gC[lvl] = d(loss)/d(C_lvl) for lvl in 3, 4, 5 (the stage outputs,

@@ -59,10 +59,12 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, *, stride: int = 1, pad: int = 0,
            mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
            out_f32: Optional[torch.Tensor] = None, want_f32: bool = False,
            out_scale: int = 1, out_hw=None, ksplit: Optional[int] = None, mask_bits: Optional[torch.Tensor] = None,
-           bits_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+           bits_out: Optional[torch.Tensor] = None, pre=None) -> torch.Tensor:
     """x [N,H,W,Cin] (NHWC), w [Cout,KH,KW,Cin] -> y [N,Ho,Wo,Cout] (or the scattered
     [N,OH,OW,Cout] tensor when out_scale > 1, which must be pre-zeroed by the caller).
-    ksplit: K slices of a long-K linear layer (None: chosen here -- the box head's FC1 is 128 tiles of 128 x 128 over K = 12544)."""
+    ksplit: K slices of a long-K linear layer (None: chosen here -- the box head's FC1 is 128 tiles of 128 x 128 over K = 12544).
+    pre = (x2, w2, scale2, shift2, stride2[, rounding]): the residual is bf16(conv1x1(x2, w2, stride2) * scale2 + shift2), formed inside this
+    launch (aldi_conv_pair_igemm; `res` stays None) -- the bits of the two launches it replaces; rounding: aldi_conv_pre_args.rounding."""
     N, H, W_, Cin = x.shape
     Cout, KH, KW, Cin2 = w.shape
     assert Cin == Cin2 and x.is_contiguous() and w.is_contiguous() and x.dtype == w.dtype, (x.shape, w.shape, x.dtype, w.dtype)
@@ -87,6 +89,13 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, *, stride: int = 1, pad: int = 0,
     a = L.ConvArgs(_p(x), _p(w), _p(out), _p(out_f32), _p(scale), _p(shift), _p(res), _p(mask),
                    N, H, W_, Cin, Cout, KH, KW, stride, pad, Ho, Wo,
                    int(relu), res_mode, out_scale, OH, OW, dtype_code(x.dtype), _p(ws), int(ksplit or 0), _p(mask_bits), _p(bits_out))
+    if pre is not None:
+        x2, w2, scale2, shift2, stride2 = pre[:5]
+        assert res is None and x2.is_contiguous() and w2.is_contiguous() and x2.dtype == x.dtype == w2.dtype and x2.shape[0] == N, (x2.shape, w2.shape)
+        assert w2.shape == (Cout, 1, 1, x2.shape[3]), (w2.shape, Cout, x2.shape)
+        q = L.ConvPreArgs(_p(x2), _p(w2), _p(scale2), _p(shift2), x2.shape[1], x2.shape[2], x2.shape[3], stride2, pre[5] if len(pre) > 5 else 0)
+        L.call("aldi_conv_pair_igemm", C.byref(a), C.byref(q), stream_ptr())
+        return out
     L.call("aldi_conv_igemm", C.byref(a), stream_ptr())
     return out_f32 if want_f32 and out is None else out
 

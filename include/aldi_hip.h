@@ -132,7 +132,11 @@ typedef struct {
     int Ho, Wo;         /* conv output grid                                               */
     int relu;           /* apply ReLU after residual                                      */
     int res_mode;       /* 0 none, 1 same index as output, 2 nearest-upsample x2 (FPN top-down:
-                           res is [N][Ho/2][Wo/2][Cout])                                   */
+                           res is [N][Ho/2][Wo/2][Cout]), 3 zero-stuffed stride 2: res is
+                           [N][(Ho+1)/2][(Wo+1)/2][Cout], added at even (ho, wo); + 0.0 at
+                           the other pixels -- the sum with a zero map that holds res at every
+                           other pixel (the data gradient of a stride-2 1x1 conv), bit for bit;
+                           odd Ho / Wo allowed; the kernel choice is mode 1's                */
     int out_scale;      /* 1 = dense output [N][Ho][Wo][Cout]; s>1 = scatter output pixel
                            (ho,wo) to (ho*s, wo*s) of an [N][OH][OW][Cout] tensor (dgrad of
                            a stride-s 1x1 conv); res/mask use the same scattered index       */
@@ -163,6 +167,28 @@ int aldi_conv_igemm_group(const aldi_conv_args* args, int n, aldi_stream_t strea
  * falls back to single launches: the last one's) to name[cap].  Launches nothing, needs no GPU, leaves aldi_last_dispatch() alone, and
  * never dereferences the tensor pointers: only which of them are null matters. */
 int aldi_conv_igemm_plan(const aldi_conv_args* args, int n, char* name, int cap);
+
+/* A 1x1 convolution whose residual is ANOTHER 1x1 convolution of a second input, both in one launch (a stage's first bottleneck: conv3 +
+ * projection shortcut; the data gradient of a stage's input: conv1's + the shortcut's):
+ *   y = act( conv(x, w) * scale + shift + bf16( conv(x2, w2) * scale2 + shift2 ) )
+ * The inner sum is rounded to bf16 exactly as a launch of its own would store it, so the result has the bits of the two launches it
+ * replaces; the [N][Ho][Wo][Cout] map between them never exists.  `a` describes the main convolution as for aldi_conv_igemm, with
+ * res = NULL and res_mode = 0.  Takes: bf16, both convolutions 1x1 without padding, the main one plain (stride 1, no mask / mask_bits /
+ * fp32 output / scatter / split-K), Cout % 64 == 0, Cin % 32 == 0 and Cin2 % 32 == 0, and x2's stride-`stride2` grid equal to the output
+ * grid; anything else is ALDI_ERR_ARG with an error text (the caller then issues two launches). */
+typedef struct {
+    const void* x2;      /* input of the inner convolution [N][H2][W2][Cin2]                          */
+    const void* w2;      /* its weight [Cout][1][1][Cin2]                                             */
+    const float* scale2; /* per-Cout multiplier, nullable = 1                                         */
+    const float* shift2; /* per-Cout addend, nullable = 0                                             */
+    int H2, W2, Cin2, stride2;
+    int rounding;        /* how the outer sum is rounded: 1 = once, bf16(acc * scale + shift + inner); 2 = twice, bf16(bf16(acc * scale +
+                            shift) + inner); 0 = as aldi_conv_igemm would round the main convolution with `res` under the current tuning
+                            knobs (its direct epilogues round once, the staged one twice)          */
+} aldi_conv_pre_args;
+int aldi_conv_pair_igemm(const aldi_conv_args* a, const aldi_conv_pre_args* pre, aldi_stream_t stream);
+/* Dry run of aldi_conv_pair_igemm, as aldi_conv_igemm_plan: same checks, status and error text; the kernel's name to name[cap]. */
+int aldi_conv_pair_igemm_plan(const aldi_conv_args* a, const aldi_conv_pre_args* pre, char* name, int cap);
 
 /* Weight gradient: dw[Cout][KH][KW][Cin] (fp32) += scale[co] * sum_pixels g[p][co] * x[pix(p,kh,kw)][ci].
  * Accumulates into dw (split-K over pixels -- ordered through `ws`, or float atomics without it -- and over micro-steps); zero dw once
