@@ -72,8 +72,10 @@ def test_bias_grad():
         gd = g.to("cuda", dt)
         db = torch.zeros(48, device="cuda")
         ops.bias_grad(gd, db)
-        ref = gd.float().cpu().sum(0)
-        assert (db.cpu() - ref).abs().max() < 1e-2 if dt == torch.bfloat16 else 1e-3
+        ref = gd.cpu().double().sum(0)
+        err = (db.cpu().double() - ref).abs().max().item()
+        # fp32: the bound of test_bias_grad_shapes (fp32 accumulation of `rows` values of unit scale)
+        assert err < (1e-2 if dt == torch.bfloat16 else 2e-5 * g.shape[0] ** 0.5 * 4), (dt, err)
 
 
 @pytest.mark.parametrize("rows,C", [(1, 8), (17, 2048), (4201, 1536), (16800, 3072), (70001, 192), (333, 6144)])
