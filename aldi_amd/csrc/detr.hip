@@ -2,8 +2,8 @@
 // off: configs/Base-DETR.yaml:56-58).  The detector's own source is an absent submodule of the reference (.gitmodules:4-6); the
 // arithmetic follows oracle/deformable_detr.py, which is pinned against transformers' implementation.
 //
-//   * GroupNorm(32) of the input projections over NHWC maps: per (image, group) statistics in two deterministic stages (partial sums per
-//     pixel chunk, chunks added in order), then one normalising pass;
+//   * GroupNorm(32) of the input projections over NHWC maps: per (image, group) statistics in two deterministic stages (sum and centred sum
+//     of squares per pixel chunk, chunks merged in order), then one normalising pass;
 //   * the glue between a deformable-attention layer's linear outputs and the sampling op: softmax over the (level, point) logits of every
 //     head and sampling locations = reference point + offset / (W_l, H_l);
 //   * multi-head self attention of the decoder's queries (a few hundred queries, 32-wide heads: one thread per query, keys and values of
@@ -34,39 +34,61 @@ __global__ __launch_bounds__(256) void dropout_add_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------- GroupNorm
-// x [N][HW][C]; part [N][chunks][G][2] = (sum, sum of squares) of the chunk's pixels over the group's C / G channels
+// x [N][HW][C]; part [N][chunks][G][2] = (sum, sum of squares ABOUT THE CHUNK'S OWN GROUP MEAN) of the chunk's pixels over the group's C / G
+// channels.  Sums of x and x * x in fp32 with E[x^2] - m^2 afterwards lose log2((mean / std)^2) bits of the variance (two digits of y at
+// mean / std = 10, and all of the variance of a group of one value); centred on the chunk's mean the squares are of the size of the
+// variance itself.  The second pass re-reads the chunk (256 pixels: L2-resident).
 __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict__ x, float* __restrict__ part, int HW, int C, int G, int chunk_px) {
-    extern __shared__ float sm[];                     // [C][2]
+    extern __shared__ float sm[];                     // [C] per-channel sums, then squares; [G] the chunk's group means
+    float* gm = sm + C;
     const int n = blockIdx.y, ch = blockIdx.x, chunks = gridDim.x;
     const int p0 = ch * chunk_px, p1 = min(HW, p0 + chunk_px);
+    const int cpg = C / G;
+    const float inv_cnt = 1.f / ((float)(p1 - p0) * (float)cpg);
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float s = 0.f, q = 0.f;
+        float s = 0.f;
         const float* col = x + ((long)n * HW + p0) * C + c;
-        for (int p = p0; p < p1; ++p, col += C) { const float v = *col; s += v; q += v * v; }
-        sm[2 * c] = s; sm[2 * c + 1] = q;
+        for (int p = p0; p < p1; ++p, col += C) s += *col;
+        sm[c] = s;
     }
     __syncthreads();
-    const int cpg = C / G;
     for (int g = threadIdx.x; g < G; g += blockDim.x) {
-        float s = 0.f, q = 0.f;
-        for (int k = 0; k < cpg; ++k) { s += sm[2 * (g * cpg + k)]; q += sm[2 * (g * cpg + k) + 1]; }
-        float* o = part + (((long)n * chunks + ch) * G + g) * 2;
-        o[0] = s; o[1] = q;
+        float s = 0.f;
+        for (int k = 0; k < cpg; ++k) s += sm[g * cpg + k];
+        part[(((long)n * chunks + ch) * G + g) * 2] = s;
+        gm[g] = s * inv_cnt;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const float m = gm[c / cpg];
+        float q = 0.f;
+        const float* col = x + ((long)n * HW + p0) * C + c;
+        for (int p = p0; p < p1; ++p, col += C) { const float d = *col - m; q += d * d; }
+        sm[c] = q;
+    }
+    __syncthreads();
+    for (int g = threadIdx.x; g < G; g += blockDim.x) {
+        float q = 0.f;
+        for (int k = 0; k < cpg; ++k) q += sm[g * cpg + k];
+        part[(((long)n * chunks + ch) * G + g) * 2 + 1] = q;
     }
 }
-__global__ void gn_stats_kernel(const float* __restrict__ part, float* __restrict__ mean, float* __restrict__ rstd, int chunks, int G, float inv_count, float eps) {
+// the chunks of an (image, group) merged in index order with the pairwise update (Chan et al.): n, mean and the sum of squares about it
+__global__ void gn_stats_kernel(const float* __restrict__ part, float* __restrict__ mean, float* __restrict__ rstd, int chunks, int G, int HW, int cpg, int chunk_px,
+                                float eps) {
     const int n = blockIdx.x;
     for (int g = threadIdx.x; g < G; g += blockDim.x) {
-        double s = 0.0, q = 0.0;                      // (a handful of chunks: the order is fixed, the width costs nothing)
+        double cnt = 0.0, m = 0.0, m2 = 0.0;          // (a handful of chunks: the order is fixed, the width costs nothing)
         for (int c = 0; c < chunks; ++c) {
             const float* o = part + (((long)n * chunks + c) * G + g) * 2;
-            s += o[0]; q += o[1];
+            const double cb = (double)(min(HW, (c + 1) * chunk_px) - c * chunk_px) * (double)cpg;
+            const double mb = (double)o[0] / cb, d = mb - m, tot = cnt + cb;
+            m += d * (cb / tot);
+            m2 += (double)o[1] + d * d * (cnt * cb / tot);
+            cnt = tot;
         }
-        const double m = s * inv_count;
-        double var = q * inv_count - m * m;
-        if (var < 0.0) var = 0.0;
         mean[n * G + g] = (float)m;
-        rstd[n * G + g] = (float)(1.0 / sqrt(var + (double)eps));
+        rstd[n * G + g] = (float)(1.0 / sqrt(m2 / cnt + (double)eps));
     }
 }
 __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -195,8 +217,8 @@ extern "C" int aldi_group_norm_forward(const float* x, const float* gamma, const
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int chunk = 256, chunks = cdiv(HW, chunk);
     float* part = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(gn_partial_kernel, dim3(chunks, N), dim3(256), (size_t)C * 2 * sizeof(float), st, x, part, HW, C, G, chunk);
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(N), dim3(64), 0, st, part, mean, rstd, chunks, G, 1.f / ((float)HW * (float)(C / G)), eps);
+    hipLaunchKernelGGL(gn_partial_kernel, dim3(chunks, N), dim3(256), (size_t)(C + G) * sizeof(float), st, x, part, HW, C, G, chunk);
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(N), dim3(64), 0, st, part, mean, rstd, chunks, G, HW, C / G, chunk, eps);
     const long total = (long)N * HW * C;
     hipLaunchKernelGGL(gn_apply_kernel, dim3((unsigned)((total / 4 + 255) / 256 < 4096 ? (total / 4 + 255) / 256 : 4096)), dim3(256), 0, st, x, mean, rstd, gamma, beta, y, total, HW, C, G);
     ALDI_CHECK_LAUNCH();
