@@ -807,7 +807,8 @@ class RCNN:
                       gt_dev: Optional[dict] = None, do_align: bool = False, labeled: bool = True,
                       da_weights: Tuple[float, float] = (0.0, 0.0)) -> Ctx:
         """GeneralizedRCNN.forward (training) + AlignMixin.forward (aldi/align.py:71-101): activations
-        and (unscaled) loss VALUES.  Gradients are produced later by ``backward(c, scales)``."""
+        and (unscaled) loss VALUES.  Gradients are produced later by ``backward(c, scales)``.  The batch is ONE chunk
+        (``c.chunks[0]``) of the records the fused step builds several of: images n0..n1, ROI rows r0..r1, its loss values."""
         N = len(images)
         st, sizes, hw = self.stage_images(images)
         shapes, geom, anchors = self.geometry(st.shape[2], st.shape[3])
@@ -816,12 +817,14 @@ class RCNN:
         c.N, c.sizes, c.hw, c.geom, c.anchors, c.gt, c.shapes = N, sizes, hw, geom, anchors, gt, shapes
         self.rpn_head(c, save=True)
         dev = self.device
+        ch = dict(n0=0, n1=N, labeled=labeled, do_align=do_align, da_weights=da_weights, align={}, distill=None)
+        c.chunks = [ch]
         # --- RPN labels + losses
         _, matched, lists, counts = self.rpn_match(geom, anchors, gt, N)
         labels, _, _, c.rpn_host_counts = self.rpn_sample(lists, counts, N)
         c.rpn_labels, c.rpn_matched, c.rpn_lists, c.rpn_counts = labels, matched, lists, counts
-        c.loss_rpn = torch.zeros(2, dtype=torch.float32, device=dev)
-        ops.rpn_loss(geom, c.head, None, anchors, labels, matched, gt["boxes"], gt["count"], GMAX, N, 1.0 / (self.p.rpn_batch * N), 0.0, 0.0, c.loss_rpn)
+        ch["loss_rpn"] = torch.zeros(2, dtype=torch.float32, device=dev)
+        ops.rpn_loss(geom, c.head, None, anchors, labels, matched, gt["boxes"], gt["count"], GMAX, N, 1.0 / (self.p.rpn_batch * N), 0.0, 0.0, ch["loss_rpn"])
         # --- proposals (detached)
         c.props, c.prop_scores, c.prop_count = self.proposals(c, geom, anchors, hw, N, training=True)
         # --- ROI heads
@@ -831,107 +834,11 @@ class RCNN:
             torch.manual_seed(roi_seed)
         self.roi_sample(c, c.props, c.prop_count, gt, N)
         self.roi_forward(c)
-        c.loss_box = torch.zeros(2, dtype=torch.float32, device=dev)
-        ops.box_loss(c.pred, self.Cp, self.K, c.R, c.rois, c.r_cls, c.r_gt, self.p.roi_weights, 0.0, 0.0, None, c.loss_box)
-        c.align = {}
-        c.distill = None
-        c.labeled, c.da_weights = labeled, da_weights
+        ch["r0"], ch["r1"] = 0, c.R
+        ch["loss_box"] = torch.zeros(2, dtype=torch.float32, device=dev)
+        ops.box_loss(c.pred, self.Cp, self.K, c.R, c.rois, c.r_cls, c.r_gt, self.p.roi_weights, 0.0, 0.0, None, ch["loss_box"])
         if do_align:
-            self.align_forward(c, labeled, da_weights)
-        return c
-
-    # ------------------------------------------------------------------ fused multi-chunk training forward
-    def forward_train_fused(self, specs: List[dict]) -> Ctx:
-        """Several micro-batches ("chunks") of the reference schedule through ONE trunk / head launch sequence
-        (FrozenBN => no cross-image coupling, so batching the source and target student
-        passes is exact).  Each spec: dict(images, instances | gt_dev, labeled, do_align, pre_rpn, pre_roi) where
-        pre_rpn / pre_roi are host callbacks fired right before that chunk's RPN / ROI sampling draws, which keeps
-        the global torch RNG stream identical to the sequential schedule.  Losses are reduced per chunk."""
-        dev = self.device
-        images = [im for sp in specs for im in sp["images"]]
-        N = len(images)
-        st, sizes, hw = self.stage_images(images)
-        shapes, geom, anchors = self.geometry(st.shape[2], st.shape[3])
-        # everything that does not need ground truth first: a chunk's GT may be the pseudo-labels of a teacher inference
-        # still running on another stream (spec["gt_wait"] joins it)
-        c = self.trunk(st, sizes, save=True)
-        c.N, c.sizes, c.hw, c.geom, c.anchors, c.shapes = N, sizes, hw, geom, anchors, shapes
-        self.rpn_head(c, save=True)
-        # proposal generation (top-k, NMS: latency-bound, a handful of workgroups) runs beside anchor matching / label
-        # compaction on the second stream; ROI preparation needs both
-        side = self._wgrad_stream()
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                c.props, c.prop_scores, c.prop_count = self.proposals(c, geom, anchors, hw, N, training=True)
-        else:
-            c.props, c.prop_scores, c.prop_count = self.proposals(c, geom, anchors, hw, N, training=True)
-        for sp in specs:
-            if sp.get("gt_lazy") is not None:              # e.g. launch the teacher now, behind the student's label-free work
-                sp["gt_dev"] = sp["gt_lazy"]()
-        for sp in specs:
-            if sp.get("gt_wait") is not None:
-                sp["gt_wait"]()
-        gts = [sp["gt_dev"] if sp.get("gt_dev") is not None else self.stage_gt(sp["instances"]) for sp in specs]
-        gt = {k: torch.cat([g[k] for g in gts]) for k in ("boxes", "classes", "count")}
-        c.gt = gt
-        _, matched, lists, counts = self.rpn_match(geom, anchors, gt, N)
-        if side is not None:
-            torch.cuda.current_stream().wait_stream(side)
-        prep = self._roi_prepare(c.props, c.prop_count, gt, N)
-        both = torch.cat([counts.view(-1), prep["counts"].view(-1), self.err.view(-1)]).cpu().tolist()      # the ONE device->host sync of the student pass
-        raise_on_error(both[-1], "student")
-        rpn_counts = [both[2 * i: 2 * i + 2] for i in range(N)]
-        roi_counts = [both[2 * N + 2 * i: 2 * N + 2 * i + 2] for i in range(N)]
-        # host draws, chunk by chunk, in the sequential schedule's order
-        rsel, rnsel, rh, osel, onsel, oh = [], [], [], [], [], []
-        n0 = 0
-        chunks = []
-        for sp in specs:
-            n1 = n0 + len(sp["images"])
-            if sp.get("pre_rpn"):
-                sp["pre_rpn"]()
-            a, b, h_ = self._sample_host(rpn_counts[n0:n1], self.p.rpn_batch, self.p.rpn_pos_frac)
-            rsel.append(a); rnsel.append(b); rh += h_
-            if sp.get("pre_roi"):
-                sp["pre_roi"]()
-            a, b, h2 = self._sample_host(roi_counts[n0:n1], self.p.roi_batch, self.p.roi_pos_frac)
-            osel.append(a); onsel.append(b); oh += h2
-            chunks.append(dict(n0=n0, n1=n1, labeled=sp.get("labeled", True), do_align=sp.get("do_align", False),
-                               da_weights=sp.get("da_weights", (0.0, 0.0)), rpn_counts=rpn_counts[n0:n1], roi_counts=roi_counts[n0:n1]))
-            n0 = n1
-        labels = torch.empty((N, anchors.shape[0]), dtype=torch.int32, device=dev)
-        rsel_d, rnsel_d, osel_d, onsel_d = ops.upload_packed([torch.cat(rsel), torch.cat(rnsel), torch.cat(osel), torch.cat(onsel)], dev)
-        ops.rpn_apply_sample(labels, anchors.shape[0], N, lists, rsel_d, rnsel_d, self.p.rpn_batch)
-        c.rpn_labels, c.rpn_matched, c.rpn_lists, c.rpn_counts = labels, matched, lists, counts
-        self._roi_gather(c, prep, osel_d, onsel_d, oh, gt, N)
-        r0 = 0
-        for ch, sp in zip(chunks, specs):                   # e.g. the teacher's box head on this chunk's ROIs, on its own stream
-            r1 = r0 + sum(c.rows[ch["n0"]:ch["n1"]])
-            if sp.get("post_rois") is not None:
-                sp["post_rois"](c, ch["n0"], r0, r1)
-            r0 = r1
-        self.roi_forward(c)
-        # per-chunk loss values
-        r0 = 0
-        for ch in chunks:
-            n0, n1 = ch["n0"], ch["n1"]
-            r1 = r0 + sum(c.rows[n0:n1])
-            ch["r0"], ch["r1"] = r0, r1
-            ch["loss_rpn"] = torch.zeros(2, dtype=torch.float32, device=dev)
-            ch["loss_box"] = torch.zeros(2, dtype=torch.float32, device=dev)
-            nc = n1 - n0
-            ops.rpn_loss(geom, [h[n0:n1] for h in c.head], None, anchors, labels[n0:n1], matched[n0:n1], gt["boxes"][n0:n1], gt["count"][n0:n1],
-                         GMAX, nc, 1.0 / (self.p.rpn_batch * nc), 0.0, 0.0, ch["loss_rpn"])
-            ops.box_loss(c.pred[r0:r1], self.Cp, self.K, r1 - r0, c.rois[r0:r1], c.r_cls[r0:r1], c.r_gt[r0:r1], self.p.roi_weights, 0.0, 0.0, None, ch["loss_box"])
-            ch["align"] = {}
-            ch["distill"] = None
-            if ch["do_align"]:
-                self._align_forward_chunk(c, ch)
-            r0 = r1
-        c.chunks = chunks
-        c.align = {}
-        c.distill = None
+            self._align_forward_chunk(c, ch)
         return c
 
     def _align_forward_chunk(self, c: Ctx, ch: dict):
@@ -965,7 +872,7 @@ class RCNN:
         return acts, self.conv(acts[-1], self.ins_da_layers[-1], want_f32=True)
 
     def distill_forward_chunk(self, c: Ctx, ch: dict, teacher_head, teacher_pred, labels, n_valid, n_fg, values=True, **kw):
-        """distillation losses of one chunk of a fused forward (teacher tensors cover exactly that chunk).  values = False: only
+        """distillation losses of one chunk (teacher tensors cover exactly that chunk).  values = False: only
         describe the losses; `backward_fused` then writes their values while it computes their gradients (ch["values_in_backward"])."""
         dev = self.device
         n0, n1, r0, r1 = ch["n0"], ch["n1"], ch["r0"], ch["r1"]
@@ -1003,8 +910,8 @@ class RCNN:
         return d
 
     def backward_fused(self, c: Ctx, scales: List[Dict[str, float]], after_losses=None):
-        """backward of forward_train_fused: per-chunk loss gradients (scales[i] for chunk i) into the shared head-gradient
-        buffers, then ONE pass heads -> FPN -> res5..res3 over all images."""
+        """backward of a context with chunks (`forward_train`: one; the fused step: several): per-chunk loss gradients w.r.t. the head
+        outputs (scales[i] for chunk i) into the shared head-gradient buffers, then ONE pass heads -> FPN -> res5..res3 over all images."""
         T, dev = self.dtype, self.device
         # The loss kernels produce value AND gradient in one pass.  Chunks flagged `values_in_backward` (the fused step) take their
         # loss values from THIS pass -- no separate value launches on the chain between the box head and the backward -- and all
@@ -1071,6 +978,7 @@ class RCNN:
                              sc("loss_cls"), sc("loss_box_reg"), c.gpred[r0:r1], l_box)
             d = ch["distill"]
             if d is not None:
+                # each kernel handles a loss pair with ONE scale: split the call when the two scales differ
                 def rpn_d(do_obj, do_reg, s_):
                     ops.rpn_distill_loss(c.geom, heads, d["t_head"], gheads, d["labels"], nc, d["obj_T"], d["n_valid"], d["n_fg"], do_obj, do_reg, s_, l_drpn,
                                          counts_dev=d.get("counts_dev"))
@@ -1120,56 +1028,26 @@ class RCNN:
             after_losses()                                   # (the loss values are final here: the caller's logging branches off)
         self._backward_trunk(c, align_list)
 
+    # the whole-batch names of the sequential driver: the batch is the one chunk `forward_train` left
     def align_forward(self, c: Ctx, labeled: bool, da_weights):
         """AlignMixin.forward (aldi/align.py:75-90): discriminators behind gradient reversal, BCE vs constant domain label."""
-        dev = self.device
-        label = 1.0 if labeled else 0.0
-        if self.has_img_da:
-            acts, pooled, logit = self._img_disc_forward(c.P[self.img_da_level])
-            c.loss_da_img = torch.zeros(1, dtype=torch.float32, device=dev)
-            ops.domain_bce(logit, logit.shape[-1], c.N, label, da_weights[0], 0.0, None, c.loss_da_img)
-            c.align["img"] = (acts, pooled, logit)
-        if self.has_ins_da and c.R > 0:
-            acts, logit = self._ins_disc_forward(c.fc2)
-            c.loss_da_ins = torch.zeros(1, dtype=torch.float32, device=dev)
-            ops.domain_bce(logit, logit.shape[-1], c.R, label, da_weights[1], 0.0, None, c.loss_da_ins)
-            c.align["ins"] = (acts, logit)
+        c.chunks[0].update(labeled=labeled, da_weights=da_weights)
+        self._align_forward_chunk(c, c.chunks[0])
 
     def distill_forward(self, c: Ctx, teacher_head: List[torch.Tensor], teacher_pred: torch.Tensor, labels: torch.Tensor,
                         n_valid: int, n_fg: int, *, obj_T: float, cls_T: float, kl: bool,
                         do_obj: bool, do_rpn_reg: bool, do_cls: bool, do_roih_reg: bool):
         """ALDIDistiller.get_rpn_losses + get_roih_losses (aldi/distill.py:193-278): loss values now, gradients in backward."""
-        dev = self.device
-        c.distill = dict(t_head=teacher_head, t_pred=teacher_pred, labels=labels, n_valid=n_valid, n_fg=n_fg, obj_T=obj_T, cls_T=cls_T,
-                         kl=kl, do_obj=do_obj, do_rpn_reg=do_rpn_reg, do_cls=do_cls, do_roih_reg=do_roih_reg)
-        c.loss_dist_rpn = torch.zeros(2, dtype=torch.float32, device=dev)
-        c.loss_dist_roi = torch.zeros(2, dtype=torch.float32, device=dev)
-        ops.rpn_distill_loss(c.geom, c.head, teacher_head, None, labels, c.N, obj_T, n_valid, n_fg, do_obj, do_rpn_reg, 0.0, c.loss_dist_rpn)
-        ops.roih_distill_loss(c.pred, teacher_pred, self.Cp, self.K, c.R, cls_T, kl, do_cls, do_roih_reg, 0.0, None, c.loss_dist_roi)
+        self.distill_forward_chunk(c, c.chunks[0], teacher_head, teacher_pred, labels, n_valid, n_fg, values=True, obj_T=obj_T, cls_T=cls_T,
+                                   kl=kl, do_obj=do_obj, do_rpn_reg=do_rpn_reg, do_cls=do_cls, do_roih_reg=do_roih_reg)
+        c.distill = c.chunks[0]["distill"]             # (what was recorded, for readers of the context: tests/test_engine_gpu.py)
 
     def loss_dict(self, c: Ctx) -> "OrderedDict[str, torch.Tensor]":
         """0-d device tensors in the key order of GeneralizedRCNN.forward (+ AlignMixin)."""
-        d = OrderedDict()
-        d["loss_cls"], d["loss_box_reg"] = c.loss_box[0], c.loss_box[1]
-        d["loss_rpn_cls"], d["loss_rpn_loc"] = c.loss_rpn[0], c.loss_rpn[1]
-        if "img" in c.align:
-            d["loss_da_img"] = c.loss_da_img[0]
-        if "ins" in c.align:
-            d["loss_da_ins"] = c.loss_da_ins[0]
-        return d
+        return self.chunk_loss_dict(c.chunks[0])
 
     def distill_loss_dict(self, c: Ctx) -> "OrderedDict[str, torch.Tensor]":
-        d = OrderedDict()
-        k = c.distill
-        if k["do_obj"]:
-            d["loss_obj_bce"] = c.loss_dist_rpn[0]
-        if k["do_rpn_reg"]:
-            d["loss_rpn_l1"] = c.loss_dist_rpn[1]
-        if k["do_cls"]:
-            d["loss_cls_ce"] = c.loss_dist_roi[0]
-        if k["do_roih_reg"]:
-            d["loss_roih_l1"] = c.loss_dist_roi[1]
-        return d
+        return self.chunk_distill_loss_dict(c.chunks[0])
 
     def _roi_prepare(self, props, prop_count, gt, N, tail=None) -> dict:
         """append GT, match (IoU >= 0.5), classes, ordered fg/bg lists + their counts (device)."""
@@ -1312,52 +1190,9 @@ class RCNN:
 
     # ------------------------------------------------------------------ backward
     def backward(self, c: Ctx, scales: Dict[str, float]):
-        """Accumulate d(sum_k scales[k] * loss_k)/d(params) into weights.grad: loss gradients w.r.t. the
-        head outputs first, then heads -> FPN -> res5..res3.  A missing / zero scale contributes
+        """Accumulate d(sum_k scales[k] * loss_k)/d(params) into weights.grad.  A missing / zero scale contributes
         nothing (the reference's `v * 0`)."""
-        W = self.wts
-        T = self.dtype
-        dev = self.device
-        sc = lambda k: float(scales.get(k, 0.0))
-        scratch = torch.zeros(2, dtype=torch.float32, device=dev)
-        c.ghead = [torch.zeros_like(h) for h in c.head]
-        c.gpred = torch.zeros((max(c.R, 1), self.Cp), dtype=torch.float32, device=dev)
-        gt = c.gt
-        ops.rpn_loss(c.geom, c.head, c.ghead, c.anchors, c.rpn_labels, c.rpn_matched, gt["boxes"], gt["count"], GMAX, c.N,
-                     1.0 / (self.p.rpn_batch * c.N), sc("loss_rpn_cls"), sc("loss_rpn_loc"), scratch)
-        ops.box_loss(c.pred, self.Cp, self.K, c.R, c.rois, c.r_cls, c.r_gt, self.p.roi_weights, sc("loss_cls"), sc("loss_box_reg"), c.gpred, scratch)
-        if c.distill is not None:
-            d = c.distill
-            # each kernel handles a loss pair with ONE scale: split the call when the two scales differ
-            def rpn_d(do_obj, do_reg, s_):
-                ops.rpn_distill_loss(c.geom, c.head, d["t_head"], c.ghead, d["labels"], c.N, d["obj_T"], d["n_valid"], d["n_fg"],
-                                     do_obj, do_reg, s_, scratch)
-
-            def roi_d(do_cls, do_reg, s_):
-                ops.roih_distill_loss(c.pred, d["t_pred"], self.Cp, self.K, c.R, d["cls_T"], d["kl"], do_cls, do_reg, s_, c.gpred, scratch)
-            if sc("loss_obj_bce") == sc("loss_rpn_l1"):
-                rpn_d(d["do_obj"], d["do_rpn_reg"], sc("loss_obj_bce"))
-            else:
-                rpn_d(d["do_obj"], False, sc("loss_obj_bce"))
-                rpn_d(False, d["do_rpn_reg"], sc("loss_rpn_l1"))
-            if sc("loss_cls_ce") == sc("loss_roih_l1"):
-                roi_d(d["do_cls"], d["do_roih_reg"], sc("loss_cls_ce"))
-            else:
-                roi_d(d["do_cls"], False, sc("loss_cls_ce"))
-                roi_d(False, d["do_roih_reg"], sc("loss_roih_l1"))
-        label = 1.0 if c.labeled else 0.0
-        if "img" in c.align:
-            acts, pooled, logit = c.align["img"]
-            glog = torch.empty(logit.shape, dtype=T, device=dev)
-            ops.domain_bce(logit, logit.shape[-1], c.N, label, c.da_weights[0], sc("loss_da_img"), glog, scratch)
-            c.align["img"] = (acts, pooled, glog)
-        if "ins" in c.align:
-            acts, logit = c.align["ins"]
-            glog = torch.empty(logit.shape, dtype=T, device=dev)
-            ops.domain_bce(logit, logit.shape[-1], c.R, label, c.da_weights[1], sc("loss_da_ins"), glog, scratch)
-            c.align["ins"] = (acts, glog)
-        al = dict(n0=0, n1=c.N, r0=0, r1=c.R, **c.align)
-        self._backward_trunk(c, [al] if c.align else [])
+        self.backward_fused(c, [scales])
 
     def _backward_trunk(self, c: Ctx, align_list: List[dict]):
         """heads -> FPN -> res5..res3 given d(loss)/d(head outputs) in c.ghead / c.gpred (fp32)."""

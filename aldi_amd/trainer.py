@@ -2,7 +2,7 @@
 aldi/dropin.py:29-184).  The iteration's schedule -- source weak/strong, target-weak alignment,
 distillation, loss-key suffixes, 1/accum scaling -- is a table (``plan_micro_steps``) executed either
 chunk by chunk (``run_model_labeled_unlabeled``, the reference's order) or as one fused student pass
-(``fused_run_model``) on the HIP engine."""
+(``fused_step.FusedStep``; ``fused_run_model_detr`` for the Deformable-DETR detector) on the HIP engine."""
 from __future__ import annotations
 
 import contextlib
@@ -162,139 +162,6 @@ def _teacher_stream(device):
         # (ALDI_TEACHER_PRIO: HIP stream priority of the teacher's branch, e.g. -1 = above the student's; measured)
         _TEACHER_STREAMS[key] = torch.cuda.Stream(device=device, priority=int(os.environ.get("ALDI_TEACHER_PRIO", "0")))
     return _TEACHER_STREAMS[key]
-
-
-def fused_run_model(trainer, labeled_weak, labeled_strong, unlabeled_weak, unlabeled_strong):
-    """MI355X-first form of `run_model_labeled_unlabeled` for the reference's FPN configurations
-    (BATCH_CONTENTS = labeled_strong [+ unlabeled_strong], one IMS_PER_GPU chunk each): the source, the
-    target-weak alignment and the distillation student passes go through ONE trunk/head launch sequence
-    (`RCNN.forward_train_fused`) and ONE backward, with a single device->host sync for the sampling counts.
-    Same loss-dict keys, values, 1/accum scaling, `v*0` masking and global-RNG stream as the sequential
-    driver (tests/test_engine_gpu.py::test_fused_step_equals_sequential)."""
-    from .model import DevicePseudoLabels
-    from .structures import as_record
-    model, dist_ = trainer.model, trainer.distiller
-    eng = model.engine
-    bs = trainer.model_batch_size
-    do_align, do_distill = _schedule_flags(trainer)
-    plan = plan_micro_steps(labeled_weak, labeled_strong, unlabeled_weak, unlabeled_strong, do_align=do_align, do_distill=do_distill)
-    total = sum(len(s_ or []) for s_ in [labeled_weak, labeled_strong, unlabeled_weak])
-    accum = total // bs
-    has_disc = do_align
-    da = model.cfg.DOMAIN_ADAPT.ALIGN
-    da_w = (da.IMG_DA_WEIGHT, da.INS_DA_WEIGHT)
-    fire_student = lambda: model.roi_heads.fire_pre()
-    specs = []
-    for row in plan:
-        if row.teacher_data is None:                # supervised / alignment rows: one chunk of the fused student pass each
-            specs.append(dict(images=[d["image"] for d in row.data], instances=[as_record(d["instances"]) for d in row.data],
-                              labeled=row.kwargs.get("labeled", True), do_align=row.kwargs.get("do_align", False), da_weights=da_w,
-                              pre_roi=fire_student))
-    tc = None
-    if do_distill:
-        if dist_.cls_loss_type not in ("CE", "KL"):
-            raise ValueError("cls_loss_type must be one of {CE, KL}")
-        teacher = dist_.teacher.module if hasattr(dist_.teacher, "module") else dist_.teacher
-        # The teacher's inference (N = 2, mostly small launches) runs on its own HIP stream beside the student's trunk / RPN head
-        # / proposal generation, none of which needs the pseudo-labels.  It is ENQUEUED after them (the engine calls
-        # `gt_lazy` once the student's label-free work is in the queue): the host needs ~3 ms to issue the teacher's launches,
-        # and issued first they would simply run alone while the student's kernels are still being queued behind them.
-        side = _teacher_stream(model.device)
-        ev0 = None
-        if side is not None:
-            ev0 = torch.cuda.Event()
-            ev0.record()                          # previous step's optimizer / EMA / readers of the teacher's outputs
-        st_ = {}
-
-        def teacher_gt():
-            if side is not None:
-                side.wait_event(ev0)
-                with torch.cuda.stream(side), torch.no_grad():
-                    st_["tc"] = teacher.engine.inference([d["image"] for d in unlabeled_weak], dist_.pseudo_label_threshold)
-            else:
-                with torch.no_grad():
-                    st_["tc"] = teacher.engine.inference([d["image"] for d in unlabeled_weak], dist_.pseudo_label_threshold)
-            return st_["tc"].pseudo
-        gt_wait = (lambda: torch.cuda.current_stream().wait_stream(side)) if side is not None else None
-
-        def pre_rpn_distill():
-            teacher.roi_heads.fire_pre()         # the teacher's eval inference re-seeds with the OLD seed (SURVEY B.3)
-            dist_.seeder.reset_seed()
-        t_out = {}
-
-        def teacher_box_head(c_, n0, r0, r1):
-            """the teacher's box head on the student's sampled proposals (aldi/distill.py:160-162), beside the student's own"""
-            rois_t = c_.rois[r0:r1].clone()
-            rois_t[:, 0] -= n0
-            if side is not None:
-                side.wait_stream(torch.cuda.current_stream())
-                rois_t.record_stream(side)
-                with torch.cuda.stream(side), torch.no_grad():
-                    t_out["pred"] = teacher.engine.box_head_on(st_["tc"], rois_t, r1 - r0)
-            else:
-                t_out["pred"] = teacher.engine.box_head_on(st_["tc"], rois_t, r1 - r0)
-        specs.append(dict(images=[d["image"] for d in unlabeled_strong], gt_lazy=teacher_gt, gt_wait=gt_wait, labeled=True, do_align=False,
-                          pre_rpn=pre_rpn_distill, pre_roi=fire_student, post_rois=teacher_box_head))
-    c = eng.forward_train_fused(specs)
-    if do_distill:
-        tc = st_["tc"]
-        teacher._last_inference = tc
-        labels_ = [DevicePseudoLabels(tc.sizes[i], tc.pseudo, i) for i in range(len(unlabeled_weak))]
-        for dw, ds, lab in zip(unlabeled_weak, unlabeled_strong, labels_):
-            dw["instances"] = lab
-            ds["instances"] = lab
-    loss_dict = {}
-    scales = []
-    entries = []
-    for ch, row in zip(c.chunks, plan):
-        name = row.name
-        losses = eng.chunk_loss_dict(ch)
-        sc = {}
-        if row.teacher_data is not None:
-            hard = {"loss_cls": dist_.do_hard_cls, "loss_rpn_cls": dist_.do_hard_obj, "loss_rpn_loc": dist_.do_hard_rpn_reg,
-                    "loss_box_reg": dist_.do_hard_roi_reg}
-            n0, n1, r0, r1 = ch["n0"], ch["n1"], ch["r0"], ch["r1"]
-            torch.manual_seed(dist_.seeder.seed)
-            eng._sample_host(ch["roi_counts"], eng.p.roi_batch, eng.p.roi_pos_frac)   # the teacher's identical ROI draws
-            if side is not None:
-                torch.cuda.current_stream().wait_stream(side)
-            t_pred = t_out["pred"]
-            labels, n_valid, n_fg, _ = eng.rpn_sample(c.rpn_lists[n0:n1], None, n1 - n0, host_counts=ch["rpn_counts"])
-            eng.distill_forward_chunk(c, ch, tc.head, t_pred, labels, n_valid, n_fg, obj_T=float(dist_.obj_temperature),
-                                      cls_T=float(dist_.cls_temperature), kl=dist_.cls_loss_type == "KL", do_obj=dist_.do_obj_dst,
-                                      do_rpn_reg=dist_.do_rpn_reg_dst, do_cls=dist_.do_cls_dst, do_roih_reg=dist_.do_roih_reg_dst)
-            out = {}
-            for k, v in losses.items():
-                out[k] = v if hard.get(k, False) else (v, 0.0)      # the reference's `v * 0.0`, applied in the batched arithmetic below
-                sc[k] = (1.0 if hard.get(k, False) else 0.0) / accum
-            if has_disc:
-                out["_da"] = torch.zeros((), device=model.device)
-            for k, v in eng.chunk_distill_loss_dict(ch).items():
-                out[k] = v
-                sc[k] = 1.0 / accum
-        else:
-            out = losses
-            sc = {k: (1.0 / accum if row.keep(k) else 0.0) for k in losses}
-        scales.append(sc)
-        for k, v in out.items():
-            if row.keep(k):
-                entries.append((f"{k}_{name}", v))
-    # loss-dict arithmetic (`v * 0.0` masking, `/ accum`) for all entries in a handful of launches instead of two or three
-    # 0-d kernels per entry (the host issues those at ~10 us apiece in the middle of the step)
-    kept = [(n_, v) for n_, v in entries if not isinstance(v, tuple)]
-    masked = [(n_, v[0]) for n_, v in entries if isinstance(v, tuple)]
-    vals = {}
-    if kept:
-        kv = (torch.stack([v for _, v in kept]) / accum).detach()
-        vals.update({n_: kv[i] for i, (n_, _) in enumerate(kept)})
-    if masked:
-        mv = ((torch.stack([v for _, v in masked]) * 0.0) / accum).detach()
-        vals.update({n_: mv[i] for i, (n_, _) in enumerate(masked)})
-    for n_, _ in entries:                                        # original key order
-        loss_dict[n_] = loss_dict[n_] + vals[n_] if n_ in loss_dict else vals[n_]
-    eng.backward_fused(c, scales)
-    model._last_fused = c
-    return loss_dict
 
 
 def _num_classes(cfg) -> int:
@@ -581,7 +448,7 @@ class _ALDITrainer:
         return why is None
 
     def _can_fuse(self, data):
-        """the fused driver takes the reference's FPN batch contents (labeled_strong [+ unlabeled weak / strong pairs]) in any whole
+        """the fused driver (`fused_step.FusedStep`, the only one for the R-CNN engines) takes the reference's FPN batch contents (labeled_strong [+ unlabeled weak / strong pairs]) in any whole
         number of IMS_PER_GPU-sized micro-batches per part -- e.g. the shipped IMS_PER_BATCH 48 / IMS_PER_GPU 2 on 8 GPUs = three
         source and three distillation micro-steps (reference configs/Base-RCNN-FPN.yaml:15-16, aldi/trainer.py:51-52) -- as long as
         the whole iteration fits one student pass (16 images: the staging kernels' limit)"""
@@ -606,8 +473,6 @@ class _ALDITrainer:
             total += len(uw)
         if total > 16:
             return False
-        if os.environ.get("ALDI_FUSED_LEGACY", "0") == "1" and (len(ls) != bs or (do_distill and len(us) != bs)):
-            return False                                     # (the older single-chunk driver, kept for A/B runs)
         return True
 
     def _can_fuse_detr(self, data) -> bool:
@@ -645,13 +510,13 @@ class _ALDITrainer:
         model = self.model.module if hasattr(self.model, "module") else self.model
         eng = getattr(model, "engine", None)
         return (bool(self.fused) and (bool(model.cfg.SOLVER.get("PIPELINE_PREFIX", False)) or os.environ.get("ALDI_PIPELINE_PREFIX") == "1") and os.environ.get("ALDI_PIPELINE_PREFIX") != "0"
-                and os.environ.get("ALDI_FUSED_LEGACY", "0") != "1" and type(eng) is RCNN and eng.prefix_pipelinable())
+                and type(eng) is RCNN and eng.prefix_pipelinable())
 
     def _defers_zero_grad(self) -> bool:
         from .engine import RCNN
         model = self.model.module if hasattr(self.model, "module") else self.model
         # (only the flat R50 weight container: the ViTDet / ConvNeXt models keep their trunk's gradients in a second buffer)
-        return bool(self.fused) and os.environ.get("ALDI_FUSED_LEGACY", "0") != "1" and type(getattr(model, "engine", None)) is RCNN
+        return bool(self.fused) and type(getattr(model, "engine", None)) is RCNN
 
     def _defers_sgd(self) -> bool:
         W = getattr(self.model, "weights", None)
@@ -684,10 +549,6 @@ class _ALDITrainer:
                 eng.grad_ready = reducer.ready
             ok = False
             try:
-                if os.environ.get("ALDI_FUSED_LEGACY", "0") == "1":
-                    out = fused_run_model(self, *data)
-                    ok = True
-                    return out
                 if getattr(self, "_fused_step", None) is None:
                     from .fused_step import FusedStep
                     self._fused_step = FusedStep(self)
@@ -909,7 +770,7 @@ class ALDITrainer(DefaultTrainer):
         super(ALDITrainer, self).before_step()
         if self.cfg.EMA.ENABLED:
             t = self._trainer
-            if getattr(t, "fused", False) and os.environ.get("ALDI_FUSED_LEGACY", "0") != "1" and type(t.model.engine).__name__ == "RCNN":
+            if getattr(t, "fused", False) and type(t.model.engine).__name__ == "RCNN":
                 # the fused step runs the tick on the teacher's stream, beside the student's forward (only the teacher's
                 # inference needs the new weights); `run_model` falls back to running it right away when it cannot fuse
                 t._pending_ema = (self.ema, self.iter)
