@@ -382,7 +382,7 @@ __global__ __launch_bounds__(256) void roialign_fwd_sep_kernel(Feats ft, const f
         int lo = ncol, hi = -1;
         for (int x = 0; x < ncol; ++x)
             if (colc[tid][x] != 0.f) { lo = min(lo, x); hi = x; }
-        xlo_s[tid] = lo; xhi_s[tid] = hi;
+        xlo_s[tid] = hi < 0 ? 0 : lo; xhi_s[tid] = hi;     // no live sample: an empty run [0, -1], whatever the sign of ncol
     }
     __syncthreads();
     if (pw >= P) return;
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256) void roialign_fwd_sep_kernel(Feats ft, const f
         int po[NP];
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
-            const int xk = min(xlo + k, xhi);
+            const int xk = max(min(xlo + k, xhi), 0);          // (an empty run re-reads pixel fx0 with weight 0, never the pixel before it)
             wcr[k] = k < run ? colc[pw][xk] : 0.f;
             po[k] = xk * C;
         }
