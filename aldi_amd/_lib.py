@@ -183,6 +183,14 @@ class FoldItem(C.Structure):
     _fields_ = [("w", c_void_p), ("scale", c_void_p), ("out", c_void_p), ("rows", c_int), ("cols", c_int), ("chunk_begin", c_int), ("reserved", c_int)]
 
 
+class ClipChunk(C.Structure):
+    """aldi_clip_chunk (include/aldi_hip.h)"""
+    _fields_ = [("start", c_int), ("len", c_int), ("seg", c_int), ("reserved", c_int)]
+
+
+NORM_L2, NORM_INF = 0, 1
+
+
 class BottleneckArgs(C.Structure):
     _fields_ = [("x", c_void_p), ("res", c_void_p), ("y", c_void_p), ("w1", c_void_p), ("w2", c_void_p), ("w3", c_void_p),
                 ("b1", c_void_p), ("b2", c_void_p), ("b3", c_void_p),

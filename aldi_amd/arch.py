@@ -272,6 +272,25 @@ class ParamLayout:
                 out.append((p.b_off, p.b_off + pad_to(p.rows, 64)))
         return out
 
+    def param_segments(self) -> List[Tuple[str, int, int]]:
+        """(state-dict key, element offset, numel) of every trainable detectron2 parameter tensor inside [0, n_train), ascending:
+        what detectron2's optimizer sees one by one (gradient clipping is per parameter).  A packed engine tensor splits into its
+        sources' row ranges; the zero padding (rows, the 64-element rounding) belongs to no segment; fc1 is permuted inside its own."""
+        out = []
+        for p in self.t.values():
+            if not p.trainable:
+                continue
+            row = p.kk * p.kk * p.cin
+            r0 = 0
+            for src in p.sources:
+                c = self.d2[src]
+                out.append((src + ".weight", p.w_off + r0 * row, c.cout * row))
+                if p.bias:
+                    out.append((src + ".bias", p.b_off + r0, c.cout))
+                r0 += c.cout
+        out.sort(key=lambda s: s[1])
+        return out
+
     def state_dict_keys(self) -> List[str]:
         keys = []
         for name, c in self.d2.items():

@@ -665,6 +665,145 @@ __global__ void sgd_dev_kernel(float* __restrict__ p, const float* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Gradient clipping over the flat SGD state (include/aldi_hip.h: segments, chunk table).  One workgroup of 256 threads per chunk
+// of at most ALDI_CLIP_CHUNK elements: scalar head up to the first 16-byte boundary, float4 body, scalar tail.
+// ------------------------------------------------------------------------------------------
+// accumulators of the two norm kinds, in double: a sum of squares (a product of two floats is exact), or a max that keeps a NaN
+template <bool L2> __device__ __forceinline__ double norm_take(double acc, float v) {
+    const double d = (double)v;
+    if (L2) return acc + d * d;
+    const double a = fabs(d);
+    return (a > acc || a != a) ? a : acc;
+}
+template <bool L2> __device__ __forceinline__ double norm_join(double a, double b) {
+    if (L2) return a + b;
+    return (b > a || b != b) ? b : a;
+}
+// fixed tree over the 64 lanes, then the waves in index order; valid in thread 0
+template <bool L2> __device__ __forceinline__ double norm_block_reduce(double v, double* sm /* 4 doubles */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = norm_join<L2>(v, __shfl_down(v, o, 64));
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double r = 0.0;
+    if (threadIdx.x == 0) {
+        r = sm[0];
+        for (int i = 1; i < 4; ++i) r = norm_join<L2>(r, sm[i]);
+    }
+    return r;
+}
+
+template <bool L2>
+__global__ __launch_bounds__(256) void seg_norm_partials_kernel(const float* __restrict__ g, const aldi_clip_chunk* __restrict__ chunks,
+                                                                 double* __restrict__ partials) {
+    __shared__ double sm[4];
+    const aldi_clip_chunk c = chunks[blockIdx.x];
+    if (c.seg < 0) return;                                   // padding belongs to no parameter (uniform over the workgroup)
+    const float* __restrict__ x = g + c.start;
+    const int tid = threadIdx.x, len = c.len;
+    int head = (4 - (c.start & 3)) & 3;
+    head = head < len ? head : len;
+    const int nv = (len - head) >> 2, tail0 = head + nv * 4;
+    double acc = 0.0;
+    if (tid < head) acc = norm_take<L2>(acc, x[tid]);
+    const float4* __restrict__ xv = reinterpret_cast<const float4*>(x + head);
+#pragma unroll 4
+    for (int q = tid; q < nv; q += 256) {
+        const float4 v = xv[q];
+        acc = norm_take<L2>(acc, v.x); acc = norm_take<L2>(acc, v.y); acc = norm_take<L2>(acc, v.z); acc = norm_take<L2>(acc, v.w);
+    }
+    if (tid < len - tail0) acc = norm_take<L2>(acc, x[tail0 + tid]);
+    const double r = norm_block_reduce<L2>(acc, sm);
+    if (tid == 0) partials[blockIdx.x] = r;
+}
+
+// one workgroup per segment: thread t joins the segment's chunks t, t + 256, ... in that order, then the fixed tree
+template <bool L2>
+__global__ __launch_bounds__(256) void seg_norm_finalize_kernel(const double* __restrict__ partials, const int* __restrict__ seg_chunks,
+                                                                 double* __restrict__ seg_acc, float* __restrict__ norm) {
+    __shared__ double sm[4];
+    const int s = blockIdx.x, first = seg_chunks[2 * s], cnt = seg_chunks[2 * s + 1];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < cnt; i += 256) acc = norm_join<L2>(acc, partials[first + i]);
+    const double r = norm_block_reduce<L2>(acc, sm);
+    if (threadIdx.x == 0) {
+        seg_acc[s] = r;
+        norm[s] = L2 ? (float)__dsqrt_rn(r) : (float)r;
+    }
+}
+
+// the whole model's norm: the segments' sums (maxima) joined in segment order by one thread
+template <bool L2>
+__global__ void global_norm_kernel(const double* __restrict__ seg_acc, int n_segs, float* __restrict__ global_norm) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double r = 0.0;
+    for (int s = 0; s < n_segs; ++s) r = norm_join<L2>(r, seg_acc[s]);
+    global_norm[0] = L2 ? (float)__dsqrt_rn(r) : (float)r;
+}
+
+// torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6); clamp(max=1.0) -- fp32, in that order.  torch evaluates
+// a Python scalar over a tensor as tensor.reciprocal() * scalar (Tensor.__rdiv__): two roundings, and so here.
+__global__ void clip_coef_kernel(const float* __restrict__ norm, const float* __restrict__ global_norm, int n_segs, float clip_value,
+                                 float gscale_abs, float* __restrict__ coef) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_segs) return;
+    const float t = (global_norm ? global_norm[0] : norm[s]) * gscale_abs;
+    const float c = (1.f / (t + 1e-6f)) * clip_value;
+    coef[s] = c < 1.f ? c : (c != c ? c : 1.f);
+}
+
+// sgd_kernel with the clip between the gradient scale and the weight decay.  VALUE: clamp to [-clip_value, clip_value] (a NaN stays, as
+// torch.clamp); else the chunk's coefficient.  A padding chunk takes coefficient 1 / an infinite clamp: g*gscale itself, sgd_kernel's bits.
+template <typename T, bool VALUE>
+__global__ __launch_bounds__(256) void sgd_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, T* __restrict__ pc,
+                                                        const aldi_clip_chunk* __restrict__ chunks, const float* __restrict__ coef,
+                                                        float clip_value, float lr, float mu, float wd, float gscale, int first) {
+    const aldi_clip_chunk c = chunks[blockIdx.x];
+    const float cf = (VALUE || c.seg < 0) ? 1.f : coef[c.seg];
+    const float cv = c.seg < 0 ? __builtin_inff() : clip_value;
+    auto update = [&](float& w, float gi, float& b) {
+        float t = gi * gscale;
+        if (VALUE) {
+            t = t < -cv ? -cv : t;
+            t = t > cv ? cv : t;
+        } else {
+            t = t * cf;
+        }
+        const float d = t + wd * w;
+        b = first ? d : mu * b + d;
+        w = w - lr * b;
+    };
+    const int tid = threadIdx.x, len = c.len;
+    const long base = c.start;
+    int head = (4 - (c.start & 3)) & 3;
+    head = head < len ? head : len;
+    const int nv = (len - head) >> 2, tail0 = head + nv * 4;
+    auto one = [&](long i) {
+        float w = p[i], b = buf[i];
+        update(w, g[i], b);
+        buf[i] = b;
+        p[i] = w;
+        if (pc) Elem<T>::st(pc + i, w);
+    };
+    if (tid < head) one(base + tid);
+    if (tid < len - tail0) one(base + tail0 + tid);
+#pragma unroll 2
+    for (int q = tid; q < nv; q += 256) {
+        const long i = base + head + 4 * q;
+        const float4 gv = *reinterpret_cast<const float4*>(g + i);
+        float4 wv = *reinterpret_cast<const float4*>(p + i);
+        float4 bv = *reinterpret_cast<const float4*>(buf + i);
+        update(wv.x, gv.x, bv.x); update(wv.y, gv.y, bv.y); update(wv.z, gv.z, bv.z); update(wv.w, gv.w, bv.w);
+        *reinterpret_cast<float4*>(buf + i) = bv;
+        *reinterpret_cast<float4*>(p + i) = wv;
+        if (pc) {
+            const float o[4] = {wv.x, wv.y, wv.z, wv.w};
+            store4(pc + i, o);
+        }
+    }
+}
+
 // reference aldi/ema.py:43-46:  t = s*(1-alpha) + t*alpha   (copy_only: t = s, aldi/ema.py:29-30)
 // tc (nullable): the compute-dtype copy of the first nc elements (the weights), written in the same pass
 template <typename T>
@@ -894,6 +1033,60 @@ extern "C" int aldi_sgd_step_dev(float* p, const float* g, float* buf, void* p_c
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (dtype == ALDI_BF16) hipLaunchKernelGGL(sgd_dev_kernel<bf16_t>, dim3(nblocks(n)), dim3(256), 0, st, p, g, buf, (bf16_t*)p_compute, n, hyper);
     else hipLaunchKernelGGL(sgd_dev_kernel<float>, dim3(nblocks(n)), dim3(256), 0, st, p, g, buf, (float*)nullptr, n, hyper);
+    ALDI_CHECK_LAUNCH();
+    return ALDI_OK;
+}
+
+extern "C" int aldi_clip_chunk_elems(void) { return ALDI_CLIP_CHUNK; }
+
+extern "C" int aldi_grad_seg_norms(const float* g, const aldi_clip_chunk* chunks, int n_chunks, const int* seg_chunks, int n_segs, int norm_kind,
+                                   double* partials, double* seg_acc, float* norm, float* global_norm, aldi_stream_t stream) {
+    if (!g || !chunks || !seg_chunks || !partials || !seg_acc || !norm || n_chunks <= 0 || n_segs <= 0)
+        return aldi_set_error_msg(ALDI_ERR_ARG, "grad_seg_norms: bad args");
+    if (reinterpret_cast<uintptr_t>(g) & 15) return aldi_set_error_msg(ALDI_ERR_ARG, "grad_seg_norms: g must be 16-byte aligned");
+    if (norm_kind != ALDI_NORM_L2 && norm_kind != ALDI_NORM_INF) return aldi_set_error_msg(ALDI_ERR_ARG, "grad_seg_norms: norm_kind is ALDI_NORM_L2 or ALDI_NORM_INF");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (norm_kind == ALDI_NORM_L2) {
+        hipLaunchKernelGGL(seg_norm_partials_kernel<true>, dim3(n_chunks), dim3(256), 0, st, g, chunks, partials);
+        hipLaunchKernelGGL(seg_norm_finalize_kernel<true>, dim3(n_segs), dim3(256), 0, st, partials, seg_chunks, seg_acc, norm);
+        if (global_norm) hipLaunchKernelGGL(global_norm_kernel<true>, dim3(1), dim3(64), 0, st, seg_acc, n_segs, global_norm);
+    } else {
+        hipLaunchKernelGGL(seg_norm_partials_kernel<false>, dim3(n_chunks), dim3(256), 0, st, g, chunks, partials);
+        hipLaunchKernelGGL(seg_norm_finalize_kernel<false>, dim3(n_segs), dim3(256), 0, st, partials, seg_chunks, seg_acc, norm);
+        if (global_norm) hipLaunchKernelGGL(global_norm_kernel<false>, dim3(1), dim3(64), 0, st, seg_acc, n_segs, global_norm);
+    }
+    ALDI_CHECK_LAUNCH();
+    return ALDI_OK;
+}
+
+extern "C" int aldi_clip_coef(const float* norm, const float* global_norm, int n_segs, float clip_value, float grad_scale, float* coef,
+                              aldi_stream_t stream) {
+    if (!norm || !coef || n_segs <= 0) return aldi_set_error_msg(ALDI_ERR_ARG, "clip_coef: bad args");
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(cdiv(n_segs, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), norm, global_norm, n_segs,
+                       clip_value, fabsf(grad_scale), coef);
+    ALDI_CHECK_LAUNCH();
+    return ALDI_OK;
+}
+
+extern "C" int aldi_sgd_step_clip(float* p, const float* g, float* buf, void* p_compute, const aldi_clip_chunk* chunks, int n_chunks, const float* coef,
+                                  float clip_value, float lr, float momentum, float weight_decay, float grad_scale, int first_step, int dtype,
+                                  aldi_stream_t stream) {
+    if (!p || !g || !buf || !chunks || n_chunks <= 0) return aldi_set_error_msg(ALDI_ERR_ARG, "sgd_step_clip: bad args");
+    if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(buf)) & 15 || reinterpret_cast<uintptr_t>(p_compute) & 7)
+        return aldi_set_error_msg(ALDI_ERR_ARG, "sgd_step_clip: p, g, buf must be 16-byte aligned, p_compute 8-byte");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool bf = dtype == ALDI_BF16;
+    bf16_t* pcb = bf ? (bf16_t*)p_compute : nullptr;
+#define ALDI_SGD_CLIP_LAUNCH(T, VALUE, PC) \
+    hipLaunchKernelGGL((sgd_clip_kernel<T, VALUE>), dim3(n_chunks), dim3(256), 0, st, p, g, buf, PC, chunks, coef, clip_value, lr, momentum, weight_decay, grad_scale, first_step)
+    if (coef) {
+        if (bf) ALDI_SGD_CLIP_LAUNCH(bf16_t, false, pcb);
+        else ALDI_SGD_CLIP_LAUNCH(float, false, (float*)nullptr);
+    } else {
+        if (bf) ALDI_SGD_CLIP_LAUNCH(bf16_t, true, pcb);
+        else ALDI_SGD_CLIP_LAUNCH(float, true, (float*)nullptr);
+    }
+#undef ALDI_SGD_CLIP_LAUNCH
     ALDI_CHECK_LAUNCH();
     return ALDI_OK;
 }

@@ -241,11 +241,27 @@ class Weights:
         """deferred scalar on the gradient (applied inside the fused optimizer kernel), e.g. 1/world after all-reduce(SUM)"""
         self._gscale = getattr(self, "_gscale", 1.0) * f
 
-    def sgd_step(self, lr: float, momentum: float = 0.9, weight_decay: float = 1e-4, grad_scale: float = 1.0):
+    def sgd_step(self, lr: float, momentum: float = 0.9, weight_decay: float = 1e-4, grad_scale: float = 1.0, clip=None):
+        """clip: None | ops.ClipSpec -- detectron2's gradient clipping of the (scaled) gradient, inside the optimizer pass"""
         n = self.layout.n_train
-        ops.sgd_step(self.master, self.grad, self.mom, self.compute if self.dtype != torch.float32 else None, n, lr, momentum,
-                     weight_decay, grad_scale * getattr(self, "_gscale", 1.0), self.first_step, self.dtype)
+        gs = grad_scale * getattr(self, "_gscale", 1.0)
+        pc = self.compute if self.dtype != torch.float32 else None
+        if clip is None:
+            ops.sgd_step(self.master, self.grad, self.mom, pc, n, lr, momentum, weight_decay, gs, self.first_step, self.dtype)
+        else:
+            ops.sgd_step_clip(self.master, self.grad, self.mom, pc, self.clip_plan(), clip, lr, momentum, weight_decay, gs, self.first_step, self.dtype)
         self._after_sgd()
+
+    def clip_plan(self):
+        """chunk table and workspaces of the clipped step over layout.param_segments(), built on first use"""
+        if getattr(self, "_clip_plan", None) is None:
+            self._clip_plan = ops.ClipPlan([(off, numel) for _, off, numel in self.layout.param_segments()], self.layout.n_train, self.device)
+        return self._clip_plan
+
+    def grad_norms(self, norm_type=2.0) -> torch.Tensor:
+        """norm of the current gradient buffer per parameter tensor, in the order (and under the names) of layout.param_segments():
+        a device tensor, no host read.  The deferred gradient scalar (scale_grad) is not applied."""
+        return ops.grad_seg_norms(self.grad, self.clip_plan(), norm_type).clone()
 
     def _after_sgd(self):
         self.first_step = False

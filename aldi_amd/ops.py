@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -425,6 +425,94 @@ def sgd_step_dev(p, g, buf, p_compute, lo: int, hi: int, hyper: torch.Tensor, dt
     """SGD over elements [lo, hi) of the flat buffers, scalars (lr, momentum, weight decay, gradient scale) from the device tensor `hyper`"""
     pc = None if p_compute is None else p_compute.data_ptr() + lo * p_compute.element_size()
     L.call("aldi_sgd_step_dev", p.data_ptr() + 4 * lo, g.data_ptr() + 4 * lo, buf.data_ptr() + 4 * lo, pc, hi - lo, _p(hyper), dtype_code(dtype), stream_ptr())
+
+
+CLIP_CHUNK = int(L.lib.aldi_clip_chunk_elems())
+
+
+class ClipSpec(NamedTuple):
+    """SOLVER.CLIP_GRADIENTS of an enabled node: clip_type "value" | "norm" (both per parameter tensor, detectron2's
+    _generate_optimizer_class_with_gradient_clipping) | "full_model" (one norm over all of them); norm_type 2.0 | inf"""
+    clip_type: str
+    clip_value: float
+    norm_type: float = 2.0
+
+
+def clip_chunk_table(segments: Sequence[Tuple[int, int]], n: int, ch: int = CLIP_CHUNK):
+    """host side of include/aldi_hip.h's chunk table.  segments = [(start, numel)], disjoint, ascending, inside [0, n)
+    -> (chunks [(start, len, seg)] in ascending address order tiling [0, n) exactly once: every segment in pieces of at most `ch`
+    elements, the complement -- padding -- in pieces with seg = -1;  seg_chunks [(first chunk, number of chunks)] per segment)"""
+    chunks, seg_chunks, pos = [], [], 0
+
+    def cut(lo, hi, seg):
+        for s in range(lo, hi, ch):
+            chunks.append((s, min(ch, hi - s), seg))
+    for i, (start, numel) in enumerate(segments):
+        if numel <= 0 or start < pos or start + numel > n:
+            raise ValueError(f"clip_chunk_table: segment {i} = [{start}, {start + numel}) is empty, out of order, overlapping or outside [0, {n})")
+        cut(pos, start, -1)
+        seg_chunks.append((len(chunks), (numel + ch - 1) // ch))
+        cut(start, start + numel, i)
+        pos = start + numel
+    cut(pos, n, -1)
+    return chunks, seg_chunks
+
+
+class ClipPlan:
+    """Gradient clipping over flat fp32 buffers of n elements whose parameters are `segments` = [(start, numel)]: owns the device chunk
+    table and the workspaces (per-chunk partials, per-segment sums, `norm`, `coef`, the global norm), all allocated here, once."""
+
+    def __init__(self, segments: Sequence[Tuple[int, int]], n: int, device):
+        assert 0 < n < 2 ** 31
+        chunks, seg_chunks = clip_chunk_table(segments, n)
+        self.n, self.n_segs, self.n_chunks = n, len(segments), len(chunks)
+        items = (L.ClipChunk * len(chunks))()
+        for it, (s, ln, seg) in zip(items, chunks):
+            it.start, it.len, it.seg, it.reserved = s, ln, seg, 0
+        self.chunks = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(device)
+        self.seg_chunks = torch.tensor(seg_chunks, dtype=torch.int32).reshape(-1).to(device)
+        self.partials = torch.zeros(len(chunks), dtype=torch.float64, device=device)
+        self.seg_acc = torch.zeros(self.n_segs, dtype=torch.float64, device=device)
+        self.norm = torch.zeros(self.n_segs, dtype=torch.float32, device=device)
+        self.coef = torch.ones(self.n_segs, dtype=torch.float32, device=device)
+        self.global_norm = torch.zeros(1, dtype=torch.float32, device=device)
+
+
+def _norm_kind(norm_type) -> int:
+    nt = float(norm_type)
+    if nt == 2.0:
+        return L.NORM_L2
+    if nt == float("inf"):
+        return L.NORM_INF
+    raise ValueError(f"norm_type must be 2.0 or inf, got {norm_type!r}")
+
+
+def grad_seg_norms(g: torch.Tensor, plan: ClipPlan, norm_type=2.0, full_model: bool = False) -> torch.Tensor:
+    """plan.norm[s] = the norm of segment s of g (aldi_grad_seg_norms: double accumulation, fixed order, bit-reproducible); full_model:
+    plan.global_norm[0] as well.  Returns plan.norm (the workspace itself)."""
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.numel() >= plan.n
+    L.call("aldi_grad_seg_norms", _p(g), _p(plan.chunks), plan.n_chunks, _p(plan.seg_chunks), plan.n_segs, _norm_kind(norm_type), _p(plan.partials),
+           _p(plan.seg_acc), _p(plan.norm), _p(plan.global_norm) if full_model else None, stream_ptr())
+    return plan.norm
+
+
+def clip_coef(plan: ClipPlan, clip_value: float, grad_scale: float = 1.0, full_model: bool = False) -> torch.Tensor:
+    """plan.coef from the norms grad_seg_norms left in the plan (aldi_clip_coef: clip_grad_norm_'s three fp32 operations)"""
+    L.call("aldi_clip_coef", _p(plan.norm), _p(plan.global_norm) if full_model else None, plan.n_segs, clip_value, grad_scale, _p(plan.coef), stream_ptr())
+    return plan.coef
+
+
+def sgd_step_clip(p, g, buf, p_compute, plan: ClipPlan, clip: ClipSpec, lr, momentum, weight_decay, grad_scale, first_step, dtype) -> None:
+    """the clipped optimizer step over [0, plan.n): for "norm" / "full_model" the norm pass, the coefficients and the update, all on the
+    device and on the current stream; for "value" the update alone.  No host read."""
+    assert min(p.numel(), g.numel(), buf.numel()) >= plan.n and (p_compute is None or p_compute.numel() >= plan.n)
+    coef = None
+    if clip.clip_type != "value":
+        full = clip.clip_type == "full_model"
+        grad_seg_norms(g, plan, clip.norm_type, full_model=full)
+        coef = clip_coef(plan, clip.clip_value, grad_scale, full_model=full)
+    L.call("aldi_sgd_step_clip", _p(p), _p(g), _p(buf), _p(p_compute), _p(plan.chunks), plan.n_chunks, _p(coef), clip.clip_value, lr, momentum,
+           weight_decay, grad_scale, int(first_step), dtype_code(dtype), stream_ptr())
 
 
 def ema_update(teacher, student, teacher_compute, n, alpha, copy_only, dtype, n_compute=None) -> None:

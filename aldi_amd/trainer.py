@@ -171,11 +171,46 @@ def _num_classes(cfg) -> int:
     return int(cfg.MODEL.ROI_HEADS.NUM_CLASSES)
 
 
+def clip_spec_from_cfg(cfg):
+    """SOLVER.CLIP_GRADIENTS -> None (no node, or ENABLED False) | ops.ClipSpec.  detectron2's maybe_add_gradient_clipping knows
+    CLIP_TYPE value | norm (per parameter tensor); full_model is the DETR wrapper's one global norm.  Values the kernels do not
+    implement are rejected, never ignored (the rule of D2Params.from_cfg)."""
+    from .ops import ClipSpec
+    node = cfg.SOLVER.get("CLIP_GRADIENTS", None)
+    if node is None or not node.get("ENABLED", False):
+        return None
+    clip_type = node.get("CLIP_TYPE", "value")
+    if clip_type not in ("value", "norm", "full_model"):
+        raise ValueError(f"SOLVER.CLIP_GRADIENTS.CLIP_TYPE must be one of value, norm, full_model, got {node.get('CLIP_TYPE')!r}")
+    raw = node.get("NORM_TYPE", 2.0)
+    try:
+        norm_type = float(raw)
+    except (TypeError, ValueError):
+        norm_type = None
+    if norm_type not in (2.0, float("inf")):
+        raise ValueError(f"SOLVER.CLIP_GRADIENTS.NORM_TYPE must be 2.0 or inf, got {raw!r}")
+    raw = node.get("CLIP_VALUE", 1.0)
+    try:
+        clip_value = float(raw)
+    except (TypeError, ValueError):
+        clip_value = float("nan")
+    if not (0.0 < clip_value < float("inf")):
+        raise ValueError(f"SOLVER.CLIP_GRADIENTS.CLIP_VALUE must be a positive finite number, got {raw!r}")
+    return ClipSpec(clip_type, clip_value, norm_type)
+
+
 class EngineSGD:
     """torch.optim.SGD-shaped handle on the fused HIP optimizer (momentum / weight decay of detectron2's build_optimizer)."""
-    def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4):
+    def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4, clip=None):
+        """clip: None | ops.ClipSpec (SOLVER.CLIP_GRADIENTS, `clip_spec_from_cfg`): shown in param_groups[0]["clip"], not checkpoint state"""
         self.model = model
         self.param_groups = [{"lr": lr, "momentum": momentum, "weight_decay": weight_decay}]
+        if clip is not None:
+            self.param_groups[0]["clip"] = clip
+
+    @property
+    def clip(self):
+        return self.param_groups[0].get("clip")
 
     def zero_grad(self, set_to_none: bool = False):
         self.model.weights.zero_grad()
@@ -187,12 +222,15 @@ class EngineSGD:
             W._after_sgd()
             return
         g = self.param_groups[0]
-        W.sgd_step(g["lr"], g["momentum"], g["weight_decay"])
+        if self.clip is None:
+            W.sgd_step(g["lr"], g["momentum"], g["weight_decay"])
+        else:
+            W.sgd_step(g["lr"], g["momentum"], g["weight_decay"], clip=self.clip)
 
     def state_dict(self):
         """checkpointable (detectron2 saves the optimizer through `trainer._trainer.optimizer`): the flat momentum buffer"""
         W = self.model.weights
-        return {"format": "aldi_amd.flat_sgd", "param_groups": [dict(g) for g in self.param_groups],
+        return {"format": "aldi_amd.flat_sgd", "param_groups": [{k: v for k, v in g.items() if k != "clip"} for g in self.param_groups],
                 "momentum_buffer": None if W._mom is None else W.mom.detach().cpu().clone(), "first_step": bool(W.first_step)}
 
     def load_state_dict(self, sd):
@@ -520,8 +558,10 @@ class _ALDITrainer:
 
     def _defers_sgd(self) -> bool:
         W = getattr(self.model, "weights", None)
-        return (self._defers_zero_grad() and isinstance(self.optimizer, EngineSGD) and not _data_parallel() and W is not None
-                and not W.first_step and os.environ.get("ALDI_SGD_IN_STEP", "0") == "1")
+        # (never while the optimizer clips: a full_model norm needs every gradient before the first update, and the per-layer-group
+        #  launches inside the backward know no coefficient -- the same rule for all three clip types)
+        return (self._defers_zero_grad() and isinstance(self.optimizer, EngineSGD) and self.optimizer.clip is None and not _data_parallel()
+                and W is not None and not W.first_step and os.environ.get("ALDI_SGD_IN_STEP", "0") == "1")
 
     def run_model(self, data):
         self._fused_done = False
@@ -616,7 +656,10 @@ class DefaultTrainer:
 
     @classmethod
     def build_optimizer(cls, cfg, model):
-        return EngineSGD(model, cfg.SOLVER.BASE_LR, cfg.SOLVER.MOMENTUM, cfg.SOLVER.WEIGHT_DECAY)
+        clip = clip_spec_from_cfg(cfg)
+        if clip is None:
+            return EngineSGD(model, cfg.SOLVER.BASE_LR, cfg.SOLVER.MOMENTUM, cfg.SOLVER.WEIGHT_DECAY)
+        return EngineSGD(model, cfg.SOLVER.BASE_LR, cfg.SOLVER.MOMENTUM, cfg.SOLVER.WEIGHT_DECAY, clip=clip)
 
     def _create_checkpointer(self, model, cfg, ckpt_cls=None):
         """aldi/dropin.py:77-82: the trainer itself (iteration, LR-scheduler hook, optimizer) is a checkpointable"""

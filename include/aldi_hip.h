@@ -332,6 +332,37 @@ int aldi_sgd_step(float* p, const float* g, float* buf, void* p_compute, long n,
  * learning-rate schedule moves.  The fused step issues one per layer group as soon as the group's weight gradients are complete,
  * beside the rest of the backward, instead of one pass over all parameters after it. */
 int aldi_sgd_step_dev(float* p, const float* g, float* buf, void* p_compute, long n, const float* hyper, int dtype, aldi_stream_t stream);
+
+/* Gradient clipping of the flat SGD state (detectron2 maybe_add_gradient_clipping: SOLVER.CLIP_GRADIENTS, applied once per parameter
+ * tensor before every step; `full_model`: one norm over all of them).  The parameters are SEGMENTS [start, start + numel) of the flat
+ * buffers.  The host cuts [0, n) into a DEVICE table of chunks in ascending address order: every segment into pieces of at most
+ * ALDI_CLIP_CHUNK elements (seg = its index), and everything no segment owns -- padding -- into pieces with seg = -1.  One workgroup
+ * works on one chunk.  seg_chunks[2 s], seg_chunks[2 s + 1] = first chunk and number of chunks of segment s (device). */
+#define ALDI_CLIP_CHUNK 4096
+typedef struct aldi_clip_chunk {
+    int start, len;          /* elements; len <= ALDI_CLIP_CHUNK */
+    int seg, reserved;       /* segment index, -1 = padding      */
+} aldi_clip_chunk;
+#define ALDI_NORM_L2 0
+#define ALDI_NORM_INF 1
+int aldi_clip_chunk_elems(void);
+/* norm[s] of every segment of g (16-byte aligned): ALDI_NORM_L2 = (float)sqrt(sum g*g) with every product and every sum in double,
+ * ALDI_NORM_INF = max |g| (a NaN stays).  Fixed order of the sums: lanes, waves, the workgroup of a chunk -> partials[n_chunks]; then the
+ * chunks of a segment in index order -> seg_acc[s] (the double sum, or the max); no atomics, so the same input gives the same bits.
+ * global_norm (nullable): sqrt of the seg_acc added in segment order, or their max.  Padding chunks are not read. */
+int aldi_grad_seg_norms(const float* g, const aldi_clip_chunk* chunks, int n_chunks, const int* seg_chunks, int n_segs, int norm_kind,
+                        double* partials, double* seg_acc, float* norm, float* global_norm, aldi_stream_t stream);
+/* torch.nn.utils.clip_grad_norm_'s coefficient, its fp32 operations in its order: t = norm * |grad_scale|; c = clip_value / (t + 1e-6f),
+ * evaluated as torch evaluates a Python scalar over a tensor, reciprocal(t + 1e-6f) * clip_value; coef = c < 1 ? c : 1 (a NaN stays, as
+ * torch.clamp(max=1)).  global_norm non-null: every coef[s] from that one norm. */
+int aldi_clip_coef(const float* norm, const float* global_norm, int n_segs, float clip_value, float grad_scale, float* coef,
+                   aldi_stream_t stream);
+/* aldi_sgd_step driven by the chunk table: d = (g*grad_scale)*coef[seg] + wd*p, or with coef == NULL (CLIP_TYPE value)
+ * d = min(max(g*grad_scale, -clip_value), clip_value) + wd*p.  Padding chunks take coefficient 1 / no clamp: the bits of aldi_sgd_step.
+ * p, g, buf 16-byte aligned, p_compute 8-byte. */
+int aldi_sgd_step_clip(float* p, const float* g, float* buf, void* p_compute, const aldi_clip_chunk* chunks, int n_chunks, const float* coef,
+                       float clip_value, float lr, float momentum, float weight_decay, float grad_scale, int first_step, int dtype,
+                       aldi_stream_t stream);
 /* EMA teacher update over the flat state (aldi/ema.py:32-57): t = s*(1-alpha) + t*alpha, or t = s.  teacher_compute (nullable,
  * dtype bf16): the compute copy of the first n_compute elements, written in the same pass. */
 int aldi_ema_update(float* teacher, const float* student, void* teacher_compute, long n, long n_compute, double alpha, int copy_only, int dtype,
