@@ -545,9 +545,10 @@ class _ALDITrainer:
 
     def _wants_lookahead(self) -> bool:
         from .engine import RCNN
+        from .fused_step import pipeline_prefix_requested
         model = self.model.module if hasattr(self.model, "module") else self.model
         eng = getattr(model, "engine", None)
-        return (bool(self.fused) and (bool(model.cfg.SOLVER.get("PIPELINE_PREFIX", False)) or os.environ.get("ALDI_PIPELINE_PREFIX") == "1") and os.environ.get("ALDI_PIPELINE_PREFIX") != "0"
+        return (bool(self.fused) and pipeline_prefix_requested(model.cfg)
                 and type(eng) is RCNN and eng.prefix_pipelinable())
 
     def _defers_zero_grad(self) -> bool:
