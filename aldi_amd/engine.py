@@ -1464,7 +1464,8 @@ class RCNN:
 
     def _rpn_sparse_finish(self, c: Ctx, gP_roi: List[torch.Tensor], sp: dict) -> List[torch.Tensor]:
         """queue the two weight gradients and scatter the rows into d(loss)/d(P_l) (ROIAlign's contribution gP_roi included: fp32
-        maps are summed in fp32 and rounded once, bf16 maps take the rows by packed bf16 atomics)"""
+        maps are summed in fp32 and rounded once; bf16 maps are finished the same atomic-free way: the one workgroup that owns a target pixel
+        sums its <= 9 contributions in fp32, adds the ROIAlign share already in the map and rounds once -- csrc/rpn_sparse.hip)"""
         T, dev = self.dtype, self.device
         self._wgrad("rpn_head_out", sp["Tm"], sp["G"], temp_x=True)
         self._wgrad("proposal_generator.rpn_head.conv", sp["X9"], sp["g_t"], flat=True, temp_x=True)
