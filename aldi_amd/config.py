@@ -182,6 +182,10 @@ def add_aldi_config(cfg: CfgNode):
     # COCO box AP of `test()` matched and accumulated on the device (aldi_amd/evaluation.py DeviceCOCOEvaluator: the host
     # evaluator's numbers, one device -> host copy per evaluation); off: Detectron2COCOEvaluatorAdapter on the host
     _C.TEST.DEVICE_EVAL = False
+    # `test()` also reports average recall (AR1 .. ARl), per-category AP-<class> / AP50-<class>, and precision / recall of the
+    # detections above DOMAIN_ADAPT.TEACHER.THRESHOLD (Prec50, Rec50: the pseudo labels the student sees), from either evaluator
+    # (aldi_amd/evaluation.py summarize_bbox); off: the six AP numbers only
+    _C.TEST.EVAL_DETAIL = False
 
     _C.EMA = CN()
     _C.EMA.ENABLED = False

@@ -6,7 +6,8 @@
 // close to them (tests/test_eval_device_gpu.py).  Three kernels:
 //   1. coco_postprocess_kernel: detector_postprocess + the XYXY -> XYWH step of the evaluator's `process`;
 //   2. coco_match_kernel: evaluate_img for one (image, category) per wave -- a lane per (area range, IoU threshold) problem;
-//   3. coco_accumulate_kernel: accumulate for one (category, area range, IoU threshold) per workgroup -- block-wide scans.
+//   3. coco_accumulate_kernel: accumulate for one (category, area range, IoU threshold) per workgroup -- block-wide scans;
+//      its Detail instantiation also counts what AR at the cuts 1 / 10 and precision / recall above a score cut are made of.
 // The orderings between them (stable sorts, segment offsets) are torch plumbing on device tensors.
 #include "common.h"
 #include "sortscan.h"
@@ -149,10 +150,28 @@ __device__ __forceinline__ int block_sum_int(int v, int* smem /* >= 16 ints */) 
 //     q[r] = max(pr[i] for i >= first i with rc[i] >= R[r])      (rc is non-decreasing)
 // is the maximum of pr over {i : rc[i] >= R[r]}: every element goes to the bucket b(i) = #{r : R[r] <= rc[i]} (a binary
 // search), buckets keep their maximum, and q[r] is the maximum over the buckets above r -- maxima of the same doubles, so exact.
+//
+// Detail (aldi_coco_accumulate_detail; the host's recall_at_cut / counts_above of the same per-image results): the same walk
+// also counts, per thread and in integers, the true positives whose rank inside their (image, category) segment is below 1
+// and below 10 (COCOeval's [:, 0:maxDet] before the concatenation) and the true / false positives whose score is above tau.
+// The four counts are summed over the block after the loop (block_sum_int) and leave as doubles: recall_at = count / npig,
+// the expression of recall[b]; tp_thr / fp_thr / num_gt_out the counts themselves.  No atomics, no floating-point sums.
+struct CocoDetail {
+    const long* rank;             // [N] position of the slot inside its segment (the order coco_match_kernel walked)
+    const double* scores;         // [N] the slot's score (a float32 value held as a double)
+    double tau;                   // a detection is above the cut iff score > tau
+    double* recall_at;            // [K][4][10][2]: cuts 1 and 10
+    double* tp_thr;               // [K][4][10]
+    double* fp_thr;               // [K][4][10]
+    double* num_gt;               // [K][4]
+};
+
+template <bool Detail>
 __global__ __launch_bounds__(256) void coco_accumulate_kernel(const long* __restrict__ perm, const int* __restrict__ cat_off,
                                                               const unsigned long long* __restrict__ mbits, const unsigned long long* __restrict__ igbits,
                                                               const int* __restrict__ num_gt, int I, int K, const double* __restrict__ rec_thrs,
-                                                              double* __restrict__ precision, double* __restrict__ recall, int* __restrict__ valid) {
+                                                              double* __restrict__ precision, double* __restrict__ recall, int* __restrict__ valid,
+                                                              CocoDetail dt) {
     __shared__ int s_scan[32];
     __shared__ double s_rec[kRecs];
     __shared__ unsigned long long s_seg[kRecs + 1];      // bit patterns of non-negative doubles order as integers
@@ -166,22 +185,40 @@ __global__ __launch_bounds__(256) void coco_accumulate_kernel(const long* __rest
     double* prow = precision + (long)b * kRecs;
     if (npig_i == 0) {                                   // the host's None: no evaluated image or no regular ground truth
         for (int i = tid; i < kRecs; i += 256) prow[i] = 0.0;
-        if (tid == 0) { recall[b] = 0.0; if (t == 0) valid[c * kAreas + a] = 0; }
+        if (tid == 0) {
+            recall[b] = 0.0;
+            if (t == 0) valid[c * kAreas + a] = 0;
+            if (Detail) {
+                dt.recall_at[2L * b] = 0.0; dt.recall_at[2L * b + 1] = 0.0;
+                dt.tp_thr[b] = 0.0; dt.fp_thr[b] = 0.0;
+                if (t == 0) dt.num_gt[c * kAreas + a] = 0.0;
+            }
+        }
         return;
     }
     const double npig = (double)npig_i, eps = 2.220446049250313e-16;     // np.spacing(1)
     const int beg = cat_off[c], n = cat_off[c + 1] - beg;
     int ctp = 0, cfp = 0;
+    int tp1 = 0, tp10 = 0, tpt = 0, fpt = 0;             // Detail: this thread's own counts
     for (int base = 0; base < n; base += 256) {
         const int i = base + tid;
         const bool in = i < n;
         bool m = false, g = false;
+        long slot = 0;
         if (in) {
-            const long slot = perm[beg + i];
+            slot = perm[beg + i];
             m = (mbits[slot] >> bit) & 1;
             g = (igbits[slot] >> bit) & 1;
         }
         const bool ftp = in && m && !g, ffp = in && !m && !g;
+        if (Detail && in) {
+            const long rk = dt.rank[slot];
+            const bool above = dt.scores[slot] > dt.tau;
+            tp1 += ftp && rk < 1;
+            tp10 += ftp && rk < 10;
+            tpt += ftp && above;
+            fpt += ffp && above;
+        }
         int ttp, tfp;
         const int rtp = block_rank(ftp, s_scan, &ttp), rfp = block_rank(ffp, s_scan, &tfp);
         if (in) {
@@ -206,6 +243,19 @@ __global__ __launch_bounds__(256) void coco_accumulate_kernel(const long* __rest
     if (tid == 0) {
         recall[b] = n ? (double)ctp / npig : 0.0;
         if (t == 0) valid[c * kAreas + a] = 1;
+    }
+    if (Detail) {
+        tp1 = block_sum_int(tp1, s_scan);
+        tp10 = block_sum_int(tp10, s_scan);
+        tpt = block_sum_int(tpt, s_scan);
+        fpt = block_sum_int(fpt, s_scan);
+        if (tid == 0) {
+            dt.recall_at[2L * b] = n ? (double)tp1 / npig : 0.0;
+            dt.recall_at[2L * b + 1] = n ? (double)tp10 / npig : 0.0;
+            dt.tp_thr[b] = (double)tpt;
+            dt.fp_thr[b] = (double)fpt;
+            if (t == 0) dt.num_gt[c * kAreas + a] = npig;
+        }
     }
 }
 
@@ -246,8 +296,24 @@ extern "C" int aldi_coco_accumulate(const long* perm, const int* cat_off, const 
     if (num_images <= 0 || num_classes <= 0) return aldi_set_error_msg(ALDI_ERR_ARG, "coco_accumulate: bad sizes");
     if (!perm || !cat_off || !matched || !dt_ignore || !num_gt || !rec_thrs || !precision || !recall || !valid)
         return aldi_set_error_msg(ALDI_ERR_ARG, "coco_accumulate: null pointer");
-    hipLaunchKernelGGL(coco_accumulate_kernel, dim3((unsigned)(num_classes * kProblems)), dim3(256), 0, static_cast<hipStream_t>(stream), perm, cat_off,
-                       matched, dt_ignore, num_gt, num_images, num_classes, rec_thrs, precision, recall, valid);
+    hipLaunchKernelGGL(coco_accumulate_kernel<false>, dim3((unsigned)(num_classes * kProblems)), dim3(256), 0, static_cast<hipStream_t>(stream), perm,
+                       cat_off, matched, dt_ignore, num_gt, num_images, num_classes, rec_thrs, precision, recall, valid, CocoDetail{});
+    ALDI_CHECK_LAUNCH();
+    return ALDI_OK;
+}
+
+extern "C" int aldi_coco_accumulate_detail(const long* perm, const int* cat_off, const unsigned long long* matched, const unsigned long long* dt_ignore,
+                                           const int* num_gt, const long* rank, const double* scores, int num_images, int num_classes,
+                                           const double* rec_thrs, double tau, double* precision, double* recall, int* valid, double* recall_at,
+                                           double* tp_thr, double* fp_thr, double* num_gt_out, aldi_stream_t stream) {
+    if (num_images <= 0 || num_classes <= 0) return aldi_set_error_msg(ALDI_ERR_ARG, "coco_accumulate_detail: bad sizes");
+    if (tau != tau) return aldi_set_error_msg(ALDI_ERR_ARG, "coco_accumulate_detail: tau is NaN");
+    if (!perm || !cat_off || !matched || !dt_ignore || !num_gt || !rank || !scores || !rec_thrs || !precision || !recall || !valid || !recall_at ||
+        !tp_thr || !fp_thr || !num_gt_out)
+        return aldi_set_error_msg(ALDI_ERR_ARG, "coco_accumulate_detail: null pointer");
+    const CocoDetail dt{rank, scores, tau, recall_at, tp_thr, fp_thr, num_gt_out};
+    hipLaunchKernelGGL(coco_accumulate_kernel<true>, dim3((unsigned)(num_classes * kProblems)), dim3(256), 0, static_cast<hipStream_t>(stream), perm,
+                       cat_off, matched, dt_ignore, num_gt, num_images, num_classes, rec_thrs, precision, recall, valid, dt);
     ALDI_CHECK_LAUNCH();
     return ALDI_OK;
 }

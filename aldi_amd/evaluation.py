@@ -4,7 +4,8 @@ Mirrors what the reference reaches through `aldi/trainer.py:166-196`: `build_eva
 (`aldi/helpers.py:65-81`, a detectron2 `COCOEvaluator` that fills in missing `iscrowd` / `area`), `test()` on the EMA model, and
 the `bbox/AP50` key `BestCheckpointer` watches.  detectron2 and pycocotools are not vendored in the reference tree (and absent
 from this image), so the metric is a restatement of pycocotools' published `COCOeval` algorithm for iouType="bbox"
-(evaluateImg greedy matching, accumulate's 101-point interpolated precision, summarize's 12 numbers); it is cross-checked
+(evaluateImg greedy matching, accumulate's 101-point interpolated precision, summarize's 12 numbers: the six AP by default, the
+six AR with `detail`, `TEST.EVAL_DETAIL`); it is cross-checked
 against an independent loop implementation in oracle/coco_eval.py and hand-computed cases -- "parity unpinned" against
 pycocotools itself.
 
@@ -87,14 +88,27 @@ def evaluate_img(dt: List[dict], gt: List[dict], area_rng, max_det: int):
     return dict(scores=np.array([d["score"] for d in dt], dtype=np.float64), matched=dtm >= 0, dt_ignore=dt_ig, num_gt=int((~g_ignore).sum()))
 
 
-def accumulate(per_img: List[Optional[dict]]):
-    """COCOeval.accumulate for one (category, area range, maxDet): -> (precision [T, R], recall [T]) or None without gt"""
+def _evaluated(per_img: List[Optional[dict]], max_det: Optional[int] = None):
+    """the images that were evaluated, each cut to its first `max_det` detections (COCOeval's `[:, 0:maxDet]`; None: no cut
+    beyond the one `evaluate_img` made), and their regular ground truth: -> (list, npig), or None where accumulate has no table"""
     ev = [e for e in per_img if e is not None]
     if not ev:
         return None
     npig = sum(e["num_gt"] for e in ev)
     if npig == 0:
         return None
+    if max_det is not None:
+        ev = [dict(e, scores=e["scores"][:max_det], matched=e["matched"][:, :max_det], dt_ignore=e["dt_ignore"][:, :max_det]) for e in ev]
+    return ev, npig
+
+
+def accumulate(per_img: List[Optional[dict]], max_det: Optional[int] = None):
+    """COCOeval.accumulate for one (category, area range, maxDet): -> (precision [T, R], recall [T]) or None without gt.
+    `max_det=m` keeps the first m detections of every image before they are concatenated."""
+    cut = _evaluated(per_img, max_det)
+    if cut is None:
+        return None
+    ev, npig = cut
     scores = np.concatenate([e["scores"] for e in ev])
     order = np.argsort(-scores, kind="mergesort")
     matched = np.concatenate([e["matched"] for e in ev], axis=1)[:, order]
@@ -123,9 +137,59 @@ def accumulate(per_img: List[Optional[dict]]):
     return precision, recall
 
 
-def coco_bbox_metrics(images: Sequence[dict], annotations: List[dict], detections: List[dict], category_ids: Sequence[int]) -> "OrderedDict[str, float]":
+def recall_at_cut(per_img: List[Optional[dict]], max_det: int):
+    """`accumulate(per_img, max_det)[1]` without the precision table (average recall needs the recall vector only): the last
+    element of a row of `tps` is the row's count, so this is the same integer over the same `npig`.  -> recall [T] or None"""
+    cut = _evaluated(per_img, max_det)
+    if cut is None:
+        return None
+    ev, npig = cut
+    matched = np.concatenate([e["matched"] for e in ev], axis=1)
+    ignore = np.concatenate([e["dt_ignore"] for e in ev], axis=1)
+    tp = np.sum(matched & ~ignore, axis=1).astype(np.float64)
+    return tp / npig if matched.shape[1] else np.zeros(len(IOU_THRS))
+
+
+def score_cut(score_thresh) -> float:
+    """tau as the comparison sees it: scores are float32 values held as doubles and `process_bbox` / `aldi_detections` compare in
+    float32, so `np.float32(score) > np.float32(tau)` is `score > float(np.float32(tau))`.  None: a cut nothing exceeds."""
+    if score_thresh is None:
+        return float("inf")
+    tau = float(np.float32(score_thresh))
+    if tau != tau:
+        raise ValueError("score_thresh is NaN")
+    return tau
+
+
+def counts_above(per_img: List[Optional[dict]], tau: float):
+    """counted (not ignored) matched / unmatched detections with score > tau: -> (tp [T], fp [T]) as doubles, or None without gt.
+    Nothing is matched again: COCO's greedy matching takes the detections in descending score order, so the flags of those
+    above a cut do not depend on those below it (tests/test_eval_detail_cpu.py matches the filtered list from scratch)."""
+    cut = _evaluated(per_img)
+    if cut is None:
+        return None
+    ev, _ = cut
+    above = np.concatenate([e["scores"] for e in ev]) > tau
+    matched = np.concatenate([e["matched"] for e in ev], axis=1)
+    ignore = np.concatenate([e["dt_ignore"] for e in ev], axis=1)
+    return (np.sum(matched & ~ignore & above[None], axis=1).astype(np.float64), np.sum(~matched & ~ignore & above[None], axis=1).astype(np.float64))
+
+
+def accumulate_detail(per_img: List[Optional[dict]], tau: float):
+    """what the detail keys of `summarize_bbox` read besides (precision, recall), for one (category, area range):
+    dict(recall_at [T, 2] at the cuts MAX_DETS[:2], tp_thr [T], fp_thr [T] above tau, num_gt) or None without gt"""
+    cut = _evaluated(per_img)
+    if cut is None:
+        return None
+    tp, fp = counts_above(per_img, tau)
+    return dict(recall_at=np.stack([recall_at_cut(per_img, m) for m in MAX_DETS[:2]], axis=1), tp_thr=tp, fp_thr=fp, num_gt=float(cut[1]))
+
+
+def coco_bbox_metrics(images: Sequence[dict], annotations: List[dict], detections: List[dict], category_ids: Sequence[int], detail: bool = False,
+                      score_thresh: Optional[float] = None, class_names: Optional[Sequence[str]] = None) -> "OrderedDict[str, float]":
     """images: dict(id); annotations: dict(image_id, category_id, bbox XYWH[, iscrowd, area, ignore]); detections:
-    dict(image_id, category_id, bbox XYWH, score) -> detectron2's `bbox` result dict (AP, AP50, AP75, APs, APm, APl in percent)"""
+    dict(image_id, category_id, bbox XYWH, score) -> detectron2's `bbox` result dict (AP, AP50, AP75, APs, APm, APl in percent);
+    `detail`: the further keys `summarize_bbox` lists"""
     maybe_add_optional_annotations(annotations)
     gts, dts = defaultdict(list), defaultdict(list)
     for a in annotations:
@@ -138,11 +202,30 @@ def coco_bbox_metrics(images: Sequence[dict], annotations: List[dict], detection
         for an, rng in AREA_RNG.items():
             per_img = [evaluate_img(dts.get((i, c), []), gts.get((i, c), []), rng, MAX_DETS[-1]) for i in img_ids]
             prec[c, an] = accumulate(per_img)
-    return summarize_bbox(prec, category_ids)
+            if detail and prec[c, an] is not None:
+                prec[c, an] += (accumulate_detail(per_img, score_cut(score_thresh)),)
+    return summarize_bbox(prec, category_ids, detail=detail, score_thresh=score_thresh, class_names=class_names)
 
 
-def summarize_bbox(prec: Dict[tuple, Optional[tuple]], category_ids: Sequence[int]) -> "OrderedDict[str, float]":
-    """COCOeval.summarize's six box numbers from {(category, area name): (precision [T, R], recall [T]) or None}"""
+def summarize_bbox(prec: Dict[tuple, Optional[tuple]], category_ids: Sequence[int], detail: bool = False, score_thresh: Optional[float] = None,
+                   class_names: Optional[Sequence[str]] = None) -> "OrderedDict[str, float]":
+    """COCOeval.summarize's six box AP numbers from {(category, area name): (precision [T, R], recall [T]) or None}.
+
+    `detail=True` (the tables then carry a third element, `accumulate_detail`'s dict) appends, in this order:
+    * AR1, AR10, AR100, ARs, ARm, ARl: COCOeval.summarize's six average-recall numbers -- 100 x the mean of recall[T] over the
+      ten IoU thresholds and the categories that have a table (NaN without one); area `all` at the cuts 1 / 10 / 100, then the
+      three area ranges at the cut 100;
+    * per category c in index order, named class_names[c] or str(c): `AP-<name>`, detectron2's per-category AP (100 x the mean of
+      the category's precision[T, R], area `all`; NaN without a table), and `AP50-<name>`, the same at IoU 0.5 -- an extension
+      of ours, detectron2 has no such key;
+    * with `score_thresh` (tau; DOMAIN_ADAPT.TEACHER.THRESHOLD in the trainer), the quality of the detections the pseudo labeler
+      keeps, at IoU 0.5, area `all`, 100 detections per image: `ScoreThr` = float(np.float32(tau)); `Prec50` = 100 x sum(TP) /
+      sum(TP + FP) and `Rec50` = 100 x sum(TP) / sum(npig), micro-averaged over the categories that have a table; then per
+      category `Prec50-<name>` = 100 x TP_c / (TP_c + FP_c) (NaN when nothing is above the cut or there is no table) and
+      `Rec50-<name>` = 100 x TP_c / npig_c.  TP_c / FP_c are the counted (not ignored) matched / unmatched detections of c with
+      np.float32(score) > np.float32(tau), npig_c the category's countable ground truth.  Categories without countable
+      ground truth are left out, as they are for AP: false positives of a class that is absent from the validation set are
+      NOT seen by Prec50 / Rec50."""
     def summarize(area="all", iou=None):
         vals = []
         for c in category_ids:
@@ -156,19 +239,49 @@ def summarize_bbox(prec: Dict[tuple, Optional[tuple]], category_ids: Sequence[in
         if not vals:
             return float("nan")
         return float(np.mean(np.stack(vals))) * 100.0
-    return OrderedDict([("AP", summarize()), ("AP50", summarize(iou=0.5)), ("AP75", summarize(iou=0.75)), ("APs", summarize("small")),
-                        ("APm", summarize("medium")), ("APl", summarize("large"))])
+    res = OrderedDict([("AP", summarize()), ("AP50", summarize(iou=0.5)), ("AP75", summarize(iou=0.75)), ("APs", summarize("small")),
+                       ("APm", summarize("medium")), ("APl", summarize("large"))])
+    if not detail:
+        return res
+    nan = float("nan")
+
+    def mean_recall(area="all", cut=None):
+        vals = [prec[c, area][1] if cut is None else prec[c, area][2]["recall_at"][:, MAX_DETS.index(cut)] for c in category_ids
+                if prec[c, area] is not None]
+        return float(np.mean(np.stack(vals))) * 100.0 if vals else nan
+    res.update([("AR1", mean_recall(cut=1)), ("AR10", mean_recall(cut=10)), ("AR100", mean_recall()), ("ARs", mean_recall("small")),
+                ("ARm", mean_recall("medium")), ("ARl", mean_recall("large"))])
+    names = [str(class_names[c]) if class_names is not None else str(c) for c in category_ids]
+    t50 = int(np.flatnonzero(np.isclose(IOU_THRS, 0.5))[0])
+    for c, name in zip(category_ids, names):
+        r = prec[c, "all"]
+        res["AP-" + name] = nan if r is None else float(np.mean(r[0])) * 100.0
+        res["AP50-" + name] = nan if r is None else float(np.mean(r[0][t50])) * 100.0
+    if score_thresh is None:
+        return res
+    counts = [None if prec[c, "all"] is None else tuple(float(prec[c, "all"][2][k][t50]) for k in ("tp_thr", "fp_thr")) + (float(prec[c, "all"][2]["num_gt"]),)
+              for c in category_ids]
+    tp, fp, npig = (sum(v[k] for v in counts if v is not None) for k in range(3))
+    res["ScoreThr"] = score_cut(score_thresh)
+    res["Prec50"] = 100.0 * tp / (tp + fp) if tp + fp > 0 else nan
+    res["Rec50"] = 100.0 * tp / npig if npig > 0 else nan
+    for v, name in zip(counts, names):
+        res["Prec50-" + name] = 100.0 * v[0] / (v[0] + v[1]) if v is not None and v[0] + v[1] > 0 else nan
+        res["Rec50-" + name] = 100.0 * v[0] / v[2] if v is not None else nan
+    return res
 
 
 class Detectron2COCOEvaluatorAdapter:
     """reset / process / evaluate with detectron2 COCOEvaluator's shapes (reference aldi/helpers.py:72-81).  `dataset_dicts`:
     detectron2-format records (file_name?, image_id, height, width, annotations=[dict(bbox XYWH_ABS or XYXY_ABS, bbox_mode,
-    category_id[, iscrowd, area])]); contiguous category ids 0..K-1."""
+    category_id[, iscrowd, area])]); contiguous category ids 0..K-1.  `detail` / `score_thresh` / `class_names` (`TEST.EVAL_DETAIL`):
+    the further keys of `summarize_bbox` -- average recall, per-category AP, precision / recall above the score cut."""
 
     def __init__(self, dataset_name: str, dataset_dicts: Sequence[dict], num_classes: int, output_dir: Optional[str] = None,
-                 distributed: bool = True):
+                 distributed: bool = True, detail: bool = False, score_thresh: Optional[float] = None, class_names: Optional[Sequence[str]] = None):
         self.dataset_name, self.output_dir, self.distributed = dataset_name, output_dir, distributed
         self.num_classes = num_classes
+        self.detail, self.score_thresh, self.class_names = bool(detail), score_thresh, class_names
         self.images = [dict(id=r["image_id"], height=r["height"], width=r["width"]) for r in dataset_dicts]
         self.annotations = []
         for r in dataset_dicts:
@@ -213,7 +326,8 @@ class Detectron2COCOEvaluatorAdapter:
                 preds = [p for part in gathered for p in part]
                 if dist.get_rank() != 0:
                     return OrderedDict()
-        res = coco_bbox_metrics(self.images, [dict(a) for a in self.annotations], preds, list(range(self.num_classes)))
+        res = coco_bbox_metrics(self.images, [dict(a) for a in self.annotations], preds, list(range(self.num_classes)), detail=self.detail,
+                                score_thresh=self.score_thresh, class_names=self.class_names)
         return OrderedDict(bbox=res)
 
 
@@ -264,14 +378,18 @@ class DeviceCOCOEvaluator:
     """`Detectron2COCOEvaluatorAdapter`'s interface and numbers with detections, matching and accumulation on the device
     (csrc/eval.hip; `TEST.DEVICE_EVAL`).  `process` appends to a device arena and launches nothing that waits for the device;
     `evaluate` runs the kernels and makes ONE device -> host copy (precision, recall, valid), which `summarize_bbox` turns into
-    the six numbers with the host's numpy expressions."""
+    the six numbers with the host's numpy expressions.  With `detail` the accumulation kernel also counts what the further keys
+    are made of (`aldi_coco_accumulate_detail`); the counts ride in the same buffer and the same copy, and the same
+    `summarize_bbox` forms the keys."""
 
     def __init__(self, dataset_name: str, dataset_dicts: Sequence[dict], num_classes: int, output_dir: Optional[str] = None,
-                 distributed: bool = True, device=None):
+                 distributed: bool = True, device=None, detail: bool = False, score_thresh: Optional[float] = None,
+                 class_names: Optional[Sequence[str]] = None):
         import torch
         from . import _lib as L
         host = Detectron2COCOEvaluatorAdapter(dataset_name, dataset_dicts, num_classes, output_dir=output_dir, distributed=distributed)
         self.dataset_name, self.output_dir, self.distributed, self.num_classes = dataset_name, output_dir, distributed, num_classes
+        self.detail, self.score_thresh, self.class_names = bool(detail), score_thresh, class_names
         self.images, self.annotations = host.images, host.annotations         # converted exactly as the adapter converts them
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self._index = {im["id"]: i for i, im in enumerate(self.images)}
@@ -353,17 +471,32 @@ class DeviceCOCOEvaluator:
                        meta.data_ptr(), n, self.num_classes, boxes.data_ptr(), scores.data_ptr(), valid.data_ptr(), ops.stream_ptr())
         return boxes, scores, classes, img, (valid != 0) & (img >= 0)
 
-    def _evaluate_device(self, arrays, mark=lambda stage: None):
+    def _layout(self, detail: bool) -> "OrderedDict[str, tuple]":
+        """{field: (offset, length)} in doubles of the buffer `_evaluate_device` returns; the detail fields follow `valid`"""
+        K, A, T, R = self.num_classes, len(AREA_RNG), len(IOU_THRS), len(REC_THRS)
+        sizes = [("precision", K * A * T * R), ("recall", K * A * T), ("valid", (K * A + 1) // 2)]
+        if detail:
+            sizes += [("recall_at", K * A * T * 2), ("tp_thr", K * A * T), ("fp_thr", K * A * T), ("num_gt", K * A)]
+        lay, off = OrderedDict(), 0
+        for k, n in sizes:
+            lay[k] = (off, n)
+            off += n
+        return lay
+
+    def _evaluate_device(self, arrays, mark=lambda stage: None, detail: Optional[bool] = None):
         """match + accumulate -> one device buffer [precision K*4*10*101 | recall K*4*10 | valid K*4 (int32)]; no host sync.
+        `detail` (None: the evaluator's own setting) appends [recall_at K*4*10*2 | tp_thr K*4*10 | fp_thr K*4*10 | num_gt K*4].
         `mark(stage)` is called after each stage has been enqueued (tools/bench_eval.py records device events there)."""
         import torch
         from . import _lib as L, ops
         boxes, scores, classes, img, valid = arrays
+        detail = self.detail if detail is None else bool(detail)
         I, K, N = len(self.images), self.num_classes, int(scores.shape[0])
         nseg = I * K
-        A, T, R = len(AREA_RNG), len(IOU_THRS), len(REC_THRS)
-        n_prec, n_rec = K * A * T * R, K * A * T
-        out = torch.zeros(n_prec + n_rec + (K * A + 1) // 2, dtype=torch.float64, device=self.device)
+        A = len(AREA_RNG)
+        lay = self._layout(detail)
+        n_prec, n_rec = lay["precision"][1], lay["recall"][1]
+        out = torch.zeros(sum(n for _, n in lay.values()), dtype=torch.float64, device=self.device)
         if nseg == 0:
             return out
         # (image, category) segments, each in stable descending score order; invalid slots go to a bucket past the last segment
@@ -392,8 +525,13 @@ class DeviceCOCOEvaluator:
         cat_off = torch.searchsorted(k2s, self._cat_bounds).to(torch.int32)
         mark("category_sorts")
         with torch.cuda.device(self.device):
-            L.call("aldi_coco_accumulate", self._ptr(perm), cat_off.data_ptr(), self._ptr(mbits), self._ptr(igbits), num_gt.data_ptr(), I, K,
-                   c["rec_thrs"].data_ptr(), out.data_ptr(), out[n_prec:].data_ptr(), out[n_prec + n_rec:].data_ptr(), ops.stream_ptr())
+            if detail:      # the same walk also counts by rank (the tensor above, indexed through perm) and by score against tau
+                L.call("aldi_coco_accumulate_detail", self._ptr(perm), cat_off.data_ptr(), self._ptr(mbits), self._ptr(igbits), num_gt.data_ptr(),
+                       self._ptr(rank), self._ptr(sscores), I, K, c["rec_thrs"].data_ptr(), score_cut(self.score_thresh), out.data_ptr(),
+                       *(out[lay[k][0]:].data_ptr() for k in ("recall", "valid", "recall_at", "tp_thr", "fp_thr", "num_gt")), ops.stream_ptr())
+            else:
+                L.call("aldi_coco_accumulate", self._ptr(perm), cat_off.data_ptr(), self._ptr(mbits), self._ptr(igbits), num_gt.data_ptr(), I, K,
+                       c["rec_thrs"].data_ptr(), out.data_ptr(), out[n_prec:].data_ptr(), out[n_prec + n_rec:].data_ptr(), ops.stream_ptr())
         mark("accumulate")
         return out
 
@@ -410,13 +548,24 @@ class DeviceCOCOEvaluator:
                 arrays = tuple(self._upload(t.numpy()) for t in merge_detection_shards(gathered))
         host = self._evaluate_device(arrays).cpu()                                       # the one device -> host copy
         K, A, T, R = self.num_classes, len(AREA_RNG), len(IOU_THRS), len(REC_THRS)
-        n_prec, n_rec = K * A * T * R, K * A * T
-        precision = host[:n_prec].numpy().reshape(K, A, T, R)
-        recall = host[n_prec:n_prec + n_rec].numpy().reshape(K, A, T)
-        valid = host[n_prec + n_rec:].view(torch.int32)[:K * A].numpy().reshape(K, A)
+        lay = self._layout(self.detail)
+        field = lambda k: host[lay[k][0]:lay[k][0] + lay[k][1]]
+        precision = field("precision").numpy().reshape(K, A, T, R)
+        recall = field("recall").numpy().reshape(K, A, T)
+        valid = field("valid").view(torch.int32)[:K * A].numpy().reshape(K, A)
         self.last = dict(precision=precision, recall=recall, valid=valid)
-        prec = {(c, an): (precision[c, ai], recall[c, ai]) if valid[c, ai] else None for c in range(K) for ai, an in enumerate(AREA_RNG)}
-        return OrderedDict(bbox=summarize_bbox(prec, list(range(K))))
+        if self.detail:
+            self.last.update(recall_at=field("recall_at").numpy().reshape(K, A, T, 2), tp_thr=field("tp_thr").numpy().reshape(K, A, T),
+                             fp_thr=field("fp_thr").numpy().reshape(K, A, T), num_gt=field("num_gt").numpy().reshape(K, A))
+
+        def table(c, ai):
+            if not valid[c, ai]:
+                return None
+            more = (dict(recall_at=self.last["recall_at"][c, ai], tp_thr=self.last["tp_thr"][c, ai], fp_thr=self.last["fp_thr"][c, ai],
+                         num_gt=float(self.last["num_gt"][c, ai])),) if self.detail else ()
+            return (precision[c, ai], recall[c, ai]) + more
+        prec = {(c, an): table(c, ai) for c in range(K) for ai, an in enumerate(AREA_RNG)}
+        return OrderedDict(bbox=summarize_bbox(prec, list(range(K)), detail=self.detail, score_thresh=self.score_thresh, class_names=self.class_names))
 
 
 def inference_on_dataset(model, data_loader, evaluator) -> "OrderedDict[str, dict]":

@@ -844,9 +844,10 @@ class ALDITrainer(DefaultTrainer):
         from .evaluation import Detectron2COCOEvaluatorAdapter, DeviceCOCOEvaluator
         if output_folder is None:
             output_folder = os.path.join(cfg.OUTPUT_DIR, "inference")
-        if cfg.TEST.get("DEVICE_EVAL", False):
-            return DeviceCOCOEvaluator(dataset_name, dataset_dicts or [], _num_classes(cfg), output_dir=output_folder)
-        return Detectron2COCOEvaluatorAdapter(dataset_name, dataset_dicts or [], _num_classes(cfg), output_dir=output_folder)
+        detail = bool(cfg.TEST.get("EVAL_DETAIL", False))        # AR, per-class AP, precision / recall above the teacher's score cut
+        kw = dict(output_dir=output_folder, detail=detail, score_thresh=cfg.DOMAIN_ADAPT.TEACHER.THRESHOLD if detail else None)
+        ev = DeviceCOCOEvaluator if cfg.TEST.get("DEVICE_EVAL", False) else Detectron2COCOEvaluatorAdapter
+        return ev(dataset_name, dataset_dicts or [], _num_classes(cfg), **kw)
 
     @classmethod
     def test(cls, cfg, model, evaluators=None):

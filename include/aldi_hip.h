@@ -655,6 +655,16 @@ int aldi_coco_match(const double* det_boxes, const int* det_off, const double* g
 int aldi_coco_accumulate(const long* perm, const int* cat_off, const unsigned long long* matched, const unsigned long long* dt_ignore,
                          const int* num_gt, int num_images, int num_classes, const double* rec_thrs, double* precision, double* recall,
                          int* valid, aldi_stream_t stream);
+/* The same accumulation (precision / recall / valid are those of the call above) plus what average recall and the precision /
+ * recall above a score cut are made of, counted in the same walk.  rank [N] = position of a slot inside its segment (the
+ * order the match call walked), scores [N] = the slots' scores; a detection is above the cut iff score > tau (tau not NaN;
+ * +inf: nothing is).  "Counted" = not ignored.  recall_at [K][4][10][2] = counted matches of rank < 1 and < 10 over the
+ * category's regular ground truth; tp_thr / fp_thr [K][4][10] = counted matched / unmatched detections above the cut, and
+ * num_gt_out [K][4] = that ground truth, as doubles (integers, exact); all 0 where valid is 0. */
+int aldi_coco_accumulate_detail(const long* perm, const int* cat_off, const unsigned long long* matched, const unsigned long long* dt_ignore,
+                                const int* num_gt, const long* rank, const double* scores, int num_images, int num_classes,
+                                const double* rec_thrs, double tau, double* precision, double* recall, int* valid, double* recall_at,
+                                double* tp_thr, double* fp_thr, double* num_gt_out, aldi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * ViTDet trunk (BASELINE cfg 4).  Replaces, for the ALDI step, the torch modules that

@@ -6,6 +6,9 @@ Prints ONE JSON line (and writes it to --out).  In one process, on the 500-image
 * device path: `DeviceCOCOEvaluator.process` over the same Instances + `evaluate()` including the final copy;
   both with a device synchronise at either end, median of --repeats runs after a warm-up; and whether the two result dicts are equal;
 * device time of the stages of one evaluation (segment sorts, match, category sorts, accumulate; device events);
+* with --detail: both evaluators with `detail=True` and `score_thresh=--score-thresh` (TEST.EVAL_DETAIL: AR, per-category AP,
+  precision / recall above the cut), `equal` over all keys, and the stage times with the detail counters on
+  (`device_stage_ms`) and off (`device_stage_ms_detail_off`) on the same detections: medians of 5 evaluations each, alternating;
 * with --trainer: wall time of one `ALDITrainer.test()` on the default synthetic validation split (N = SYNTHETIC.VAL_IMAGES = 8
   images) with TEST.DEVICE_EVAL off and on, same weights -- stated for those 8 images, not extrapolated."""
 import argparse
@@ -53,7 +56,7 @@ def same(a, b):
     return list(a) == list(b) and all(a[k] == b[k] or (a[k] != a[k] and b[k] != b[k]) for k in a)
 
 
-def stages(dev, feed):
+def stages(dev, feed, detail=None):
     dev.reset()
     for inputs, outputs in feed:
         dev.process(inputs, outputs)
@@ -66,9 +69,21 @@ def stages(dev, feed):
     mark("start")
     arrays = dev._compact()
     mark("postprocess")
-    dev._evaluate_device(arrays, mark).cpu()
+    dev._evaluate_device(arrays, mark, detail=detail).cpu()
     torch.cuda.synchronize()
     return {n: round(marks[i][1].elapsed_time(e), 4) for i, (n, e) in enumerate(marks[1:])}
+
+
+def stages_on_off(dev, feed, repeats=5):
+    """-> (detail on, detail off): per-stage medians of `repeats` evaluations each, alternating, after one warm-up of both"""
+    runs = {False: [], True: []}
+    for k in range(repeats + 1):
+        for detail in (False, True):
+            r = stages(dev, feed, detail)
+            if k:
+                runs[detail].append(r)
+    med = lambda rs: {n: round(statistics.median(r[n] for r in rs), 4) for n in rs[0]}
+    return med(runs[True]), med(runs[False])
 
 
 def trainer_test(repeats=3):
@@ -104,18 +119,26 @@ def main():
     ap.add_argument("--classes", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--trainer", action="store_true")
+    ap.add_argument("--detail", action="store_true")
+    ap.add_argument("--score-thresh", type=float, default=0.8)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     records, feed = scene(a.images, a.classes)
-    host = Detectron2COCOEvaluatorAdapter("val", records, a.classes, distributed=False)
-    dev = DeviceCOCOEvaluator("val", records, a.classes, distributed=False)
+    kw = dict(detail=True, score_thresh=a.score_thresh) if a.detail else {}
+    host = Detectron2COCOEvaluatorAdapter("val", records, a.classes, distributed=False, **kw)
+    dev = DeviceCOCOEvaluator("val", records, a.classes, distributed=False, **kw)
     d_med, d_all, d_res = timed(dev, feed, max(5, a.repeats))
     h_med, h_all, h_res = timed(host, feed, max(5, a.repeats))
     out = {"bench": "eval_device", "gpu": torch.cuda.get_device_name(0), "images": a.images, "classes": a.classes,
            "ground_truth": sum(len(r["annotations"]) for r in records), "detections": sum(len(o[0]) for _, o in feed),
            "host_ms": round(h_med * 1e3, 2), "device_ms": round(d_med * 1e3, 2), "host_over_device": round(h_med / d_med, 1),
            "host_runs_ms": [round(t * 1e3, 1) for t in h_all], "device_runs_ms": [round(t * 1e3, 2) for t in d_all],
-           "equal": same(h_res["bbox"], d_res["bbox"]), "bbox": dict(d_res["bbox"]), "device_stage_ms": stages(dev, feed)}
+           "equal": same(h_res["bbox"], d_res["bbox"]), "bbox": dict(d_res["bbox"])}
+    if a.detail:
+        out["detail"], out["keys"] = True, len(d_res["bbox"])
+        out["device_stage_ms"], out["device_stage_ms_detail_off"] = stages_on_off(dev, feed)
+    else:
+        out["device_stage_ms"] = stages(dev, feed)
     if a.trainer:
         out["trainer_test"] = trainer_test()
     line = json.dumps(out)
