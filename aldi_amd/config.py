@@ -244,6 +244,12 @@ def add_aldi_config(cfg: CfgNode):
     _C.SOLVER.GRAD_PAYLOAD = "fp32"       # data-parallel gradient exchange: "fp32" (exact) or "bf16" (half the bytes per xGMI link; sums in bf16)
     _C.SOLVER.GRAD_EXCHANGE = "auto"        # per bucket: "all_reduce" or "rs_ag" (reduce_scatter_tensor + all_gather_into_tensor, aldi_amd/reduce.py);
                                             # "auto" = rs_ag on the 8 ranks of one fully connected xGMI node, all_reduce otherwise
+    # Training metrics (aldi_amd/events.py): 0 = off (nothing is created or launched); N > 0 = the losses and the head
+    # statistics of every iteration go into a device ring and reach the host every N iterations (metrics.json in OUTPUT_DIR + one console
+    # line; detectron2's writers correspond to 20).  The non-finite-loss check reads the ring at every flush, and a flush precedes every
+    # checkpoint and evaluation: a NaN / inf loss raises FloatingPointError at most N - 1 iterations late (1 = detectron2's timing) and
+    # always before anything is saved from it.
+    _C.SOLVER.LOG_PERIOD = 0
 
     # Deformable-DETR (the reference's absent submodule adds these through its own add_deformable_detr_config; configs/Base-DETR.yaml)
     _C.MODEL.DEFORMABLE_DETR = CN()

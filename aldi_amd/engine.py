@@ -395,6 +395,9 @@ class Ctx(dict):
 
 class RCNN:
     p = D2Params()          # (subclasses that do not go through this constructor run on detectron2's defaults)
+    # events.HeadStatSink | None: with a sink attached (SOLVER.LOG_PERIOD > 0) the launches that produce a micro-step's loss VALUES are
+    # followed by aldi_rpn_label_counts / aldi_box_cls_stats on the same stream with the same inputs; None: the launch sequence has neither
+    stats_sink = None
 
     def __init__(self, weights: Weights, num_classes: int, params: Optional[D2Params] = None):
         self.wts = weights
@@ -841,6 +844,10 @@ class RCNN:
         c.rpn_labels, c.rpn_matched, c.rpn_lists, c.rpn_counts = labels, matched, lists, counts
         ch["loss_rpn"] = torch.zeros(2, dtype=torch.float32, device=dev)
         ops.rpn_loss(geom, c.head, None, anchors, labels, matched, gt["boxes"], gt["count"], GMAX, N, 1.0 / (self.p.rpn_batch * N), 0.0, 0.0, ch["loss_rpn"])
+        sink = self.stats_sink
+        stat_name = sink.current if sink is not None else None      # (the sequential driver names the micro-step; nobody did: no statistics)
+        if stat_name is not None:
+            sink.rpn(stat_name, labels)
         # --- proposals (detached)
         c.props, c.prop_scores, c.prop_count = self.proposals(c, geom, anchors, hw, N, training=True)
         # --- ROI heads
@@ -853,6 +860,8 @@ class RCNN:
         ch["r0"], ch["r1"] = 0, c.R
         ch["loss_box"] = torch.zeros(2, dtype=torch.float32, device=dev)
         ops.box_loss(c.pred, self.Cp, self.K, c.R, c.rois, c.r_cls, c.r_gt, self.p.roi_weights, 0.0, 0.0, None, ch["loss_box"])
+        if stat_name is not None:
+            sink.box(c.pred, self.K, c.r_cls, [(stat_name, 0, c.R)])
         if do_align:
             self._align_forward_chunk(c, ch)
         return c
@@ -969,6 +978,7 @@ class RCNN:
         # the box head's losses of all chunks (+ RoI distillation + the compute-dtype copy of the gradient rows) as ONE launch: csrc/roi.hip
         box_fused = [] if (c.R > 0 and len(c.chunks) <= 8 and self.Cp % 2 == 0 and os.environ.get("ALDI_BOX_LOSS_FUSED", "1") == "1") else None
         c.gpred_lo = None
+        sink, stat_rows = self.stats_sink, []
         for ci, (ch, sc_) in enumerate(zip(c.chunks, scales)):
             sc = lambda k: float(sc_.get(k, 0.0))
             n0, n1, r0, r1 = ch["n0"], ch["n1"], ch["r0"], ch["r1"]
@@ -987,6 +997,12 @@ class RCNN:
             with rpn_ctx():
                 ops.rpn_loss(c.geom, heads, gheads, c.anchors, c.rpn_labels[n0:n1], c.rpn_matched[n0:n1], gt["boxes"][n0:n1], gt["count"][n0:n1],
                              GMAX, nc, 1.0 / (self.p.rpn_batch * nc), sc("loss_rpn_cls"), sc("loss_rpn_loc"), l_rpn)
+                # head statistics of the chunks whose loss values come from THIS pass (the fused step's; `forward_train` counted its own),
+                # for the micro-steps that report the detection losses (not the alignment-only pass over unlabeled images)
+                stat_name = ch.get("name") if (sink is not None and ch.get("values_in_backward") and ch["keep"]("loss_cls")) else None
+                if stat_name is not None:
+                    sink.rpn(stat_name, c.rpn_labels[n0:n1])
+                    stat_rows.append((stat_name, r0, r1))
             if box_fused is not None:
                 box_fused.append(dict(r0=r0, r1=r1, gs_cls=sc("loss_cls"), gs_box=sc("loss_box_reg"), loss_box=l_box))
             else:
@@ -1038,6 +1054,8 @@ class RCNN:
             if T == torch.bfloat16:
                 c.gpred_lo = torch.empty((c.R, self.Cp), dtype=T, device=dev)
             ops.box_losses_fused(c.pred, self.Cp, self.K, c.rois, c.r_cls, c.r_gt, self.p.roi_weights, box_fused, c.gpred, c.gpred_lo)
+        if stat_rows and c.R > 0:
+            sink.box(c.pred, self.K, c.r_cls, stat_rows)
         if early is not None:
             torch.cuda.current_stream().wait_stream(aux0)    # (the RPN-side values and head gradients: finished long ago)
         if after_losses is not None:

@@ -1062,6 +1062,15 @@ class FusedStep:
             return plan_chunks(plan_micro_steps(*data, do_align=do_align, do_distill=do_distill), bs, (da.IMG_DA_WEIGHT, da.INS_DA_WEIGHT))
         sp = planned((labeled_weak, labeled_strong, unlabeled_weak, unlabeled_strong))
         accum = sum(len(s_ or []) for s_ in (labeled_weak, labeled_strong, unlabeled_weak)) // bs
+        sink = getattr(eng, "stats_sink", None)
+        if sink is not None:
+            # head statistics (SOLVER.LOG_PERIOD): the counting launches sit beside the loss kernels of phase B (engine.backward_fused, by chunk
+            # name: recorded into the graphs); the image count per micro-step suffix is host knowledge of this plan.  Chunks of one suffix add up.
+            images = {}
+            for ch in sp.chunks:
+                if ch["keep"]("loss_cls"):
+                    images[ch["name"]] = images.get(ch["name"], 0) + ch["n1"] - ch["n0"]
+            sink.set_images(images)
         if do_distill and dist_.cls_loss_type not in ("CE", "KL"):
             raise ValueError("cls_loss_type must be one of {CE, KL}")
         self.teacher = teacher = (dist_.teacher.module if hasattr(dist_.teacher, "module") else dist_.teacher) if do_distill else None

@@ -771,3 +771,44 @@ def project2(X: torch.Tensor, mean: torch.Tensor, comp: torch.Tensor, out: Optio
         out = torch.empty((n, 2), dtype=torch.float32, device=X.device)
     L.call("aldi_project2", _p(X), n, Cc, _p(mean), _p(comp), _p(out), stream_ptr())
     return out
+
+
+# ---- training metrics (csrc/trainstats.hip; aldi_amd/events.py)
+METRICS_MAX_FLOATS, METRICS_MAX_INTS, STATS_MAX_RANGES = 64, 32, 8
+BOX_STAT_NAMES = ("num_instances", "num_accurate", "num_fg", "fg_num_accurate", "num_false_negative")
+
+
+def metrics_record(src_f: Sequence[torch.Tensor], src_i: Sequence[torch.Tensor], ring_f: torch.Tensor, ring_i: torch.Tensor,
+                   ring_iter: torch.Tensor, slot: int, iteration: int, first_bad_iter: torch.Tensor, clear_counters: bool = False) -> None:
+    """one launch: ring_f[slot][j] = *src_f[j], ring_i[slot][j] = *src_i[j] (bit for bit; src_* are one-element fp32 / int32 device
+    tensors, whose addresses travel in the launch's arguments), ring_iter[slot] = iteration; clear_counters: every *src_i[j] = 0 afterwards;
+    first_bad_iter (int32 [1]) becomes `iteration` when a float value is not finite and it is still -1"""
+    nf, ni = len(src_f), len(src_i)
+    slots = ring_f.shape[0]
+    assert ring_f.dtype == torch.float32 and tuple(ring_f.shape) == (slots, METRICS_MAX_FLOATS) and ring_f.is_contiguous()
+    assert ring_i.dtype == torch.int32 and tuple(ring_i.shape) == (slots, METRICS_MAX_INTS) and ring_i.is_contiguous()
+    assert ring_iter.dtype == torch.int32 and ring_iter.numel() == slots and first_bad_iter.dtype == torch.int32
+    assert all(t.dtype == torch.float32 and t.numel() == 1 for t in src_f) and all(t.dtype == torch.int32 and t.numel() == 1 for t in src_i)
+    fa = (C.c_void_p * max(nf, 1))(*[t.data_ptr() for t in src_f])
+    ia = (C.c_void_p * max(ni, 1))(*[t.data_ptr() for t in src_i])
+    L.call("aldi_metrics_record", fa, nf, ia, ni, int(bool(clear_counters)), _p(ring_f), _p(ring_i), _p(ring_iter), int(slot), slots,
+           int(iteration), _p(first_bad_iter), stream_ptr())
+
+
+def box_cls_stats(pred: torch.Tensor, K: int, cls: torch.Tensor, ranges: Sequence[Tuple[int, int, torch.Tensor]]) -> None:
+    """detectron2's _log_classification_stats as counts: for every (r0, r1, out) of `ranges`, out (int32 [5], BOX_STAT_NAMES) += the counts
+    of rows r0 .. r1 of pred [R][Cp] (fp32 / bf16; class scores in columns 0 .. K) against the sampled classes cls [R]"""
+    R, Cp = pred.shape
+    assert pred.is_contiguous() and cls.dtype == torch.int32 and cls.is_contiguous() and cls.numel() >= R
+    n = len(ranges)
+    assert all(o.dtype == torch.int32 and o.numel() >= 5 and o.is_contiguous() for _, _, o in ranges)
+    r0 = (C.c_int * max(n, 1))(*[int(r[0]) for r in ranges])
+    r1 = (C.c_int * max(n, 1))(*[int(r[1]) for r in ranges])
+    out = (C.c_void_p * max(n, 1))(*[r[2].data_ptr() for r in ranges])
+    L.call("aldi_box_cls_stats", _p(pred), Cp, int(K), R, _p(cls), r0, r1, out, n, dtype_code(pred.dtype), stream_ptr())
+
+
+def rpn_label_counts(labels: torch.Tensor, out: torch.Tensor) -> None:
+    """out (int32 [2]) += (number of 1, number of 0) of the sampled RPN labels [N][L] (int32 in {-1, 0, 1})"""
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and labels.dim() == 2 and out.dtype == torch.int32 and out.numel() >= 2
+    L.call("aldi_rpn_label_counts", _p(labels), labels.shape[0], labels.shape[1], _p(out), stream_ptr())

@@ -76,15 +76,27 @@ def run_model_labeled_unlabeled(trainer, labeled_weak, labeled_strong, unlabeled
         debug_dict.update(last_labeled_weak=copy.deepcopy(labeled_weak), last_labeled_strong=copy.deepcopy(labeled_strong),
                           last_unlabeled_weak=copy.deepcopy(unlabeled_weak), last_unlabeled_strong=copy.deepcopy(unlabeled_strong))
     metrics: Dict[str, torch.Tensor] = {}
+    # head statistics (SOLVER.LOG_PERIOD): the engine counts beside its loss kernels for the micro-step named here (those that report the
+    # detection losses); chunks of one micro-step add their counts and their images
+    sink = getattr(getattr(getattr(trainer.model, "module", trainer.model), "engine", None), "stats_sink", None)
+    if sink is not None:
+        sink.set_images({})
     for row in plan:
         if row.teacher_data is not None:
             assert len(row.teacher_data) == len(row.data), "Teacher and student data must be the same length."
         for lo in range(0, len(row.data), bs):
             chunk = row.data[lo:lo + bs]
-            if row.teacher_data is not None:
-                losses = trainer.distiller(row.teacher_data[lo:lo + bs], chunk)
-            else:
-                losses = trainer.model(chunk, **row.kwargs)
+            if sink is not None and row.keep("loss_cls"):
+                sink.current = row.name
+                sink.add_images(row.name, len(chunk))
+            try:
+                if row.teacher_data is not None:
+                    losses = trainer.distiller(row.teacher_data[lo:lo + bs], chunk)
+                else:
+                    losses = trainer.model(chunk, **row.kwargs)
+            finally:
+                if sink is not None:
+                    sink.current = None
             if early:               # non-contributing losses still enter the graph with weight 0 (every parameter gets a gradient)
                 trainer.do_backward(sum(v if row.keep(k) else v * 0 for k, v in losses.items()) / accum, override=True)
             for k, v in losses.items():
@@ -350,6 +362,9 @@ class WarmupMultiStepLR:
 
 class SimpleTrainer:
     """One iteration = fetch, zero_grad, run_model, backward, (all-reduce), optimizer step (aldi/dropin.py:87-130)."""
+    iter = 0                                         # set by the owning trainer before every run_step (detectron2: self._trainer.iter)
+    metric_recorder = None                           # events.DeviceMetricRecorder when SOLVER.LOG_PERIOD > 0 (DefaultTrainer._setup_metrics)
+
     def __init__(self, model, data_loader, optimizer, zero_grad_before_forward=False):
         self.model, self.data_loader, self.optimizer = model, data_loader, optimizer
         self._data_loader_iter_obj = None
@@ -440,8 +455,12 @@ class SimpleTrainer:
             self.model.weights.scale_grad(1.0 / dist.get_world_size())
 
     def _write_metrics(self, loss_dict, data_time):
+        """the reference reads every loss with .item() here (a host wait per step); with a recorder the values go into its device ring by
+        one launch on the current stream -- the step's last loss is final, no graph is being captured -- and reach the host at the flush"""
         self.last_loss_dict = loss_dict
         self.last_data_time = data_time
+        if self.metric_recorder is not None:
+            self.metric_recorder.record(loss_dict, None, self.iter, data_time=data_time)
 
 
 class AMPTrainer(SimpleTrainer):
@@ -627,6 +646,8 @@ class ALDISimpleTrainer(_ALDITrainer, SimpleTrainer):
 
 class DefaultTrainer:
     """Constructor sequence of the reference's DefaultTrainer (aldi/dropin.py:35-70) without the Detectron2 hook zoo."""
+    metric_recorder = None                           # events.DeviceMetricRecorder when SOLVER.LOG_PERIOD > 0 (_setup_metrics)
+
     def __init__(self, cfg):
         self.cfg = cfg
         model = self.build_model(cfg)
@@ -639,9 +660,40 @@ class DefaultTrainer:
         self.start_iter = 0
         self.iter = 0
         self.max_iter = cfg.SOLVER.MAX_ITER
+        self._setup_metrics(cfg)
 
     def _create_trainer(self, cfg, model, data_loader, optimizer):
         return (AMPTrainer if cfg.SOLVER.AMP.ENABLED else SimpleTrainer)(model, data_loader, optimizer)
+
+    def _setup_metrics(self, cfg):
+        """SOLVER.LOG_PERIOD > 0: the device recorder (every rank: its flush is collective under data parallelism), the event storage and --
+        main process only -- the console and metrics.json writers; the R-CNN engine gets the recorder's sink BEFORE the first step, so that
+        the step graphs are captured with the statistics launches.  0: nothing is created, the step is launched exactly as without this."""
+        period = int(cfg.SOLVER.get("LOG_PERIOD", 0) or 0)
+        if period <= 0:
+            return
+        from .events import CommonMetricPrinter, DeviceMetricRecorder, EventStorage, JSONWriter
+        model = self._trainer.model
+        core = getattr(model, "module", model)
+        device = torch.device(getattr(core, "device", None) or cfg.MODEL.DEVICE)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        rec = DeviceMetricRecorder(period, device, max_iter=self.max_iter)
+        rec.storage = self.storage = EventStorage(self.start_iter)
+        if self._is_main_process():
+            rec.writers.append(CommonMetricPrinter(self.max_iter))
+            if cfg.OUTPUT_DIR:
+                rec.writers.append(JSONWriter(os.path.join(cfg.OUTPUT_DIR, "metrics.json")))
+        self.metric_recorder = self._trainer.metric_recorder = rec
+        eng = getattr(core, "engine", None)
+        if eng is not None and hasattr(type(eng), "stats_sink"):
+            eng.stats_sink = rec.sink
+
+    def flush_metrics(self):
+        """the open logging window -> storage and writers; raises FloatingPointError when a recorded loss was not finite.  Called every
+        LOG_PERIOD iterations, after the last one, and as the first statement of everything that persists or judges state."""
+        if self.metric_recorder is not None:
+            self.metric_recorder.flush()
 
     def create_ddp_model(self, model, broadcast_buffers, cfg):
         """One process per GPU; gradients are all-reduced over RCCL in SimpleTrainer.after_backward.  Rank 0's weights are broadcast once."""
@@ -706,6 +758,7 @@ class DefaultTrainer:
         pass
 
     def run_step(self):
+        self._trainer.iter = self.iter
         self._trainer.run_step()
 
     def _is_main_process(self):
@@ -714,15 +767,25 @@ class DefaultTrainer:
     def after_step(self):
         """LRScheduler hook, then detectron2's PeriodicCheckpointer (fvcore): `model_{iter:07d}` every SOLVER.CHECKPOINT_PERIOD
         iterations and `model_final` after the last one, main process only."""
+        rec = self.metric_recorder
+        if rec is not None:
+            now = time.perf_counter()
+            rec.note_step(time_s=now - self.__dict__.get("_t_after_step", now), lr=float(self._trainer.optimizer.param_groups[0]["lr"]))
+            self._t_after_step = now
         self.scheduler.step()
         period = int(self.cfg.SOLVER.get("CHECKPOINT_PERIOD", 0) or 0)
+        last = self.iter >= self.max_iter - 1
+        save_now = period > 0 and (self.iter + 1) % period == 0 and not last
+        if rec is not None and ((self.iter + 1) % rec.period == 0 or last or save_now):
+            self.flush_metrics()                     # (every rank; before any checkpoint: a non-finite loss raises here, nothing is saved from it)
         if self._is_main_process() and self.cfg.OUTPUT_DIR:
-            if period > 0 and (self.iter + 1) % period == 0 and self.iter < self.max_iter - 1:
+            if save_now:
                 self.checkpointer.save("model_{:07d}".format(self.iter), iteration=self.iter)
-            if self.iter >= self.max_iter - 1:
+            if last:
                 self.checkpointer.save("model_final", iteration=self.iter)
 
     def train(self):
+        self._t_after_step = time.perf_counter()     # `time` of the first iteration counts from here
         for self.iter in range(self.start_iter, self.max_iter):
             self.before_step()
             self.run_step()
@@ -873,6 +936,7 @@ class ALDITrainer(DefaultTrainer):
         period = self.cfg.TEST.EVAL_PERIOD
         last = self.iter >= self.max_iter - 1
         if period > 0 and ((self.iter + 1) % period == 0 or last):
+            self.flush_metrics()                     # before the evaluation and `_model_best`: a non-finite loss raises here
             self._last_eval_results = self.test(self.cfg, self.ema.model if self.cfg.EMA.ENABLED else self.model)
             names = list(self.cfg.DATASETS.TEST) or ["synthetic_val"]
             if not self._is_main_process():

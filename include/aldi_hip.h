@@ -855,6 +855,29 @@ int aldi_moments_accum(const float* X, int n, const int* n_dev, int n_cap, int C
                        aldi_stream_t stream);
 int aldi_project2(const float* X, long n, int C, const double* mean, const double* comp, float* Y, aldi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Training metrics (csrc/trainstats.hip; aldi_amd/events.py): the loss values and the head statistics of detectron2's
+ * _log_classification_stats / RPN label counts stay on the device and reach the host once per logging window.
+ * aldi_metrics_record: ONE small launch appends one row to a device ring of `slots` rows.  src_f: nf <= ALDI_METRICS_MAX_FLOATS HOST
+ *   pointers to fp32 device scalars, src_i: ni <= ALDI_METRICS_MAX_INTS host pointers to int32 device counters (both arrays are copied
+ *   into the launch's arguments: nothing is uploaded).  ring_f[slot][j] = *src_f[j] and ring_i[slot][j] = *src_i[j] bit for bit (columns
+ *   past nf / ni are written 0), ring_iter[slot] = iteration; clear_i != 0 then writes 0 to every *src_i[j] (the counters of the next
+ *   step start from 0 without a fill launch).  If a float value is not finite and *first_bad_iter is still -1 it becomes `iteration`.
+ *   No summation on the device.  ring_f [slots][ALDI_METRICS_MAX_FLOATS] fp32, ring_i [slots][ALDI_METRICS_MAX_INTS] int32.
+ * aldi_box_cls_stats: pred [R][Cp] in `dtype` (class scores = columns 0 .. K, K = background), cls [R] the sampled classes; for each
+ *   of the nranges <= ALDI_STATS_MAX_RANGES row ranges [r0[i], r1[i]) (host arrays; an empty range adds nothing) out[i][0..5) +=
+ *   {num_instances, num_accurate, num_fg, fg_num_accurate, num_false_negative}: prediction = argmax over columns 0 .. K (the first
+ *   maximum wins, a NaN counts as the maximum), foreground = 0 <= cls < K, accurate = prediction == cls, false negative = foreground
+ *   predicted K.  out: nranges HOST pointers to 5 device int32 each.  Integer atomics: the sums do not depend on the order.
+ * aldi_rpn_label_counts: labels [N][L] int32 in {-1, 0, 1} (contiguous); out[0] += number of 1, out[1] += number of 0.
+ * ------------------------------------------------------------------------------------------------------------------ */
+enum { ALDI_METRICS_MAX_FLOATS = 64, ALDI_METRICS_MAX_INTS = 32, ALDI_STATS_MAX_RANGES = 8 };
+int aldi_metrics_record(const float* const* src_f, int nf, int* const* src_i, int ni, int clear_i, float* ring_f, int* ring_i, int* ring_iter,
+                        int slot, int slots, int iteration, int* first_bad_iter, aldi_stream_t stream);
+int aldi_box_cls_stats(const void* pred, int Cp, int K, int R, const int* cls, const int* r0, const int* r1, int* const* out, int nranges,
+                       int dtype, aldi_stream_t stream);
+int aldi_rpn_label_counts(const int* labels, int N, int L, int* out, aldi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
