@@ -15,6 +15,7 @@ Same class names / constructor arguments as the reference; `apply_image` takes a
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 import random
 from typing import List, Optional, Sequence, Tuple
@@ -469,3 +470,290 @@ def strong_views(weak_views: Sequence[torch.Tensor], augs, chw: bool = True, np_
         return launch_strong_views(weak_views, params, chw, out_chw)
     with torch.cuda.stream(stream):
         return launch_strong_views(weak_views, params, chw, out_chw)
+
+
+# ------------------------------------------------------------------------------------------------ weak views (geometry)
+# detectron2's weak chain -- `utils.build_augmentation(cfg, is_train)`: ResizeShortestEdge, then RandomFlip (reference
+# aldi/aug.py:16-37) -- on the device (csrc/geom.hip).  As above only the DRAWS and the small tables stay on the host.  The
+# resize is Pillow's `Image.resize(BILINEAR)` for uint8 (detectron2 ResizeTransform.apply_image): the coefficient arithmetic
+# below is Pillow's precompute_coeffs / normalize_coeffs_8bpc in its operation order and is pinned to Pillow's bytes by
+# tests/golden/pil_bilinear.npz.  The detectron2 pieces (output shape, draw order, box transform) restate the published v0.6
+# behaviour: PARITY UNPINNED, as oracle/aug_ops.py labels its detectron2 half.
+_GEOM_CHW_IN, _GEOM_CHW_OUT, _GEOM_HFLIP, _GEOM_FUSED = 1, 2, 4, 8
+_GEOM_TH, _GEOM_TW = 16, 64
+_PRECISION_BITS = 32 - 8 - 2
+
+
+class _GeomDesc(ctypes.Structure):
+    """aldi_geom_desc (include/aldi_hip.h)"""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("tmp", ctypes.c_void_p),
+                ("h", ctypes.c_int), ("w", ctypes.c_int), ("new_h", ctypes.c_int), ("new_w", ctypes.c_int), ("flags", ctypes.c_int),
+                ("xk_off", ctypes.c_int), ("xb_off", ctypes.c_int), ("xks", ctypes.c_int),
+                ("yk_off", ctypes.c_int), ("yb_off", ctypes.c_int), ("yks", ctypes.c_int),
+                ("tile_begin", ctypes.c_int), ("h_begin", ctypes.c_int), ("v_begin", ctypes.c_int)]
+
+
+class ResizeShortestEdge:
+    """detectron2 ResizeShortestEdge (parity unpinned): the short side becomes a drawn size, the long side follows and is
+    capped at `max_size`.  `get_params` draws from `np_rng` as `get_transform` draws from np.random."""
+    def __init__(self, short_edge_length, max_size=2 ** 31 - 1, sample_style="range"):
+        if sample_style not in ("range", "choice"):
+            raise ValueError(f"ResizeShortestEdge: sample_style {sample_style!r} is neither 'range' nor 'choice'")
+        if isinstance(short_edge_length, int):
+            short_edge_length = (short_edge_length, short_edge_length)
+        short_edge_length = tuple(int(s) for s in short_edge_length)
+        if sample_style == "range" and len(short_edge_length) != 2:
+            raise ValueError(f"ResizeShortestEdge: short_edge_length must be two values with sample_style 'range', got {short_edge_length}")
+        self.short_edge_length, self.max_size, self.sample_style = short_edge_length, max_size, sample_style
+        self.is_range = sample_style == "range"
+
+    @staticmethod
+    def get_output_shape(oldh: int, oldw: int, short_edge_length: int, max_size: int) -> Tuple[int, int]:
+        h, w = oldh, oldw
+        size = short_edge_length * 1.0
+        scale = size / min(h, w)
+        if h < w:
+            newh, neww = size, scale * w
+        else:
+            newh, neww = scale * h, size
+        if max(newh, neww) > max_size:
+            scale = max_size * 1.0 / max(newh, neww)
+            newh, neww = newh * scale, neww * scale
+        return int(newh + 0.5), int(neww + 0.5)
+
+    def get_params(self, h: int, w: int, np_rng=np.random) -> Tuple[int, int]:
+        if self.is_range:
+            size = int(np_rng.randint(self.short_edge_length[0], self.short_edge_length[1] + 1))
+        else:
+            size = int(np_rng.choice(self.short_edge_length))
+        if size == 0:
+            return h, w
+        return self.get_output_shape(h, w, size, self.max_size)
+
+
+class RandomFlip:
+    """detectron2 RandomFlip (parity unpinned): one uniform(0, 1) draw against `prob`; the device path flips horizontally only."""
+    def __init__(self, prob=0.5, *, horizontal=True, vertical=False):
+        if horizontal and vertical:
+            raise ValueError("RandomFlip: cannot do both horizontal and vertical")
+        if not horizontal and not vertical:
+            raise ValueError("RandomFlip: at least one of horizontal or vertical has to be True")
+        if vertical:
+            raise ValueError("RandomFlip: the device weak view (AUG.DEVICE_WEAK) flips horizontally only")
+        self.prob, self.horizontal, self.vertical = prob, horizontal, vertical
+
+    def get_params(self, np_rng=np.random) -> bool:
+        return bool(np_rng.uniform(0, 1.0) < self.prob)
+
+
+def get_weak_augs(cfg, is_train: bool) -> list:
+    """detectron2 `utils.build_augmentation(cfg, is_train)`: [ResizeShortestEdge] + [RandomFlip] when training and
+    INPUT.RANDOM_FLIP is not "none".  What the device path does not run is refused by name."""
+    inp = cfg.INPUT
+    if inp.get("CROP", {}).get("ENABLED", False):
+        raise ValueError("AUG.DEVICE_WEAK: INPUT.CROP.ENABLED is not supported by the device weak view (resize and horizontal flip only)")
+    flip = inp.get("RANDOM_FLIP", "horizontal")
+    if flip == "vertical":
+        raise ValueError('AUG.DEVICE_WEAK: INPUT.RANDOM_FLIP "vertical" is not supported by the device weak view (horizontal or none)')
+    if flip not in ("horizontal", "none"):
+        raise ValueError(f"AUG.DEVICE_WEAK: unknown INPUT.RANDOM_FLIP {flip!r}")
+    if is_train:
+        min_size, max_size, style = inp.MIN_SIZE_TRAIN, inp.MAX_SIZE_TRAIN, inp.get("MIN_SIZE_TRAIN_SAMPLING", "choice")
+    else:
+        min_size, max_size, style = inp.MIN_SIZE_TEST, inp.MAX_SIZE_TEST, "choice"
+    augs = [ResizeShortestEdge(min_size if isinstance(min_size, int) else tuple(min_size), max_size, style)]
+    if is_train and flip != "none":
+        augs.append(RandomFlip(horizontal=True))
+    return augs
+
+
+class WeakParams:
+    """what one image's pass through the weak chain drew: (h, w) -> (new_h, new_w), then flipped left-right or not"""
+    __slots__ = ("h", "w", "new_h", "new_w", "flip")
+
+    def __init__(self, h: int, w: int, new_h: int, new_w: int, flip: bool = False):
+        self.h, self.w, self.new_h, self.new_w, self.flip = int(h), int(w), int(new_h), int(new_w), bool(flip)
+
+    def __eq__(self, other):
+        return isinstance(other, WeakParams) and all(getattr(self, s) == getattr(other, s) for s in self.__slots__)
+
+    def __repr__(self):
+        return f"WeakParams({self.h}, {self.w}, {self.new_h}, {self.new_w}, flip={self.flip})"
+
+
+def draw_weak_params(augs, h: int, w: int, np_rng=np.random) -> WeakParams:
+    """consume `np_rng` as detectron2's AugmentationList does for one h x w image: the size draw, then the flip draw"""
+    if isinstance(np_rng, np.random.Generator):
+        raise TypeError("draw_weak_params: pass np.random or a RandomState, not a numpy Generator")
+    new_h, new_w, flip = int(h), int(w), False
+    for a in augs:
+        if isinstance(a, ResizeShortestEdge):
+            new_h, new_w = a.get_params(new_h, new_w, np_rng)
+        elif isinstance(a, RandomFlip):
+            flip ^= a.get_params(np_rng)
+        else:
+            raise ValueError(f"draw_weak_params: {type(a).__name__} is not a stage of get_weak_augs")
+    return WeakParams(h, w, new_h, new_w, flip)
+
+
+@functools.lru_cache(maxsize=256)
+def resize_tables(insz: int, outsz: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Pillow's bilinear coefficients of one axis insz -> outsz: (k int32 [outsz, ksize] with PRECISION_BITS = 22 fractional
+    bits, zero past the tap count; bounds int32 [outsz, 2] = (xmin, tap count)).  ImagingResample's precompute_coeffs +
+    normalize_coeffs_8bpc in doubles, in their operation order; the normalising sum runs over the taps left to right."""
+    insz, outsz = int(insz), int(outsz)
+    if insz < 1 or outsz < 1:
+        raise ValueError(f"resize_tables: sizes must be positive, got {insz} -> {outsz}")
+    scale = insz / outsz
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ss = 1.0 / filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(outsz, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), insz)
+    n = xmax - xmin
+    wts = np.zeros((outsz, ksize), dtype=np.float64)
+    ww = np.zeros(outsz, dtype=np.float64)
+    for x in range(ksize):
+        a = np.abs(((x + xmin).astype(np.float64) - center + 0.5) * ss)
+        col = np.where((a < 1.0) & (x < n), 1.0 - a, 0.0)
+        wts[:, x] = col
+        ww = ww + col                                        # (sequential, as the C loop adds them: np.sum may pair terms)
+    nz = ww != 0.0
+    wts[nz] = wts[nz] / ww[nz, None]
+    k = (0.5 + wts * float(1 << _PRECISION_BITS)).astype(np.int64).astype(np.int32)
+    k[np.arange(ksize)[None, :] >= n[:, None]] = 0
+    bounds = np.stack([xmin, n], axis=1).astype(np.int32)
+    k.setflags(write=False)
+    bounds.setflags(write=False)
+    return k, bounds
+
+
+def _image_layout(img: torch.Tensor, p: WeakParams, chw_in: Optional[bool]) -> bool:
+    """True when `img` is (3, h, w), False when (h, w, 3); the parameters' raw size decides, `chw_in` settles a (3, 3, 3) image"""
+    if not (img.dtype == torch.uint8 and img.dim() == 3):
+        raise ValueError("weak_views expects uint8 images of three dimensions")
+    hwc, chw = tuple(img.shape) == (p.h, p.w, 3), tuple(img.shape) == (3, p.h, p.w)
+    if chw_in is not None and (chw if chw_in else hwc):
+        return bool(chw_in)
+    if chw_in is None and (hwc or chw):
+        return not hwc
+    raise ValueError(f"weak_views: image of shape {tuple(img.shape)} for parameters drawn for {p.h}x{p.w}")
+
+
+def launch_weak_views(images: Sequence[torch.Tensor], params: Sequence[WeakParams], chw_out: bool = True,
+                      chw_in=None, outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """the device half of `weak_views`: one pinned upload (descriptors + tables), then one to three launches on the current
+    stream -- the fused kernel, and the two-pass arm for the images aldi_geom_plan keeps off it.  `outs`: the caller's own
+    output tensors (contiguous, of the output shapes) instead of fresh ones.  `chw_in`: None = each image's layout is read off its
+    shape and its parameters' raw size; a bool, or one per image, settles it."""
+    n = len(images)
+    if n == 0:
+        return []
+    if len(params) != n:
+        raise ValueError("launch_weak_views: one WeakParams per image")
+    layouts = []
+    for v, p, c in zip(images, params, chw_in if isinstance(chw_in, (list, tuple)) else [chw_in] * n):
+        layouts.append(_image_layout(v, p, c))
+        if not (v.is_cuda and v.is_contiguous()):
+            raise ValueError("launch_weak_views expects contiguous CUDA images")
+        if min(p.h, p.w, p.new_h, p.new_w) < 1:
+            raise ValueError(f"launch_weak_views: empty image in {p}")
+    # the tables of the batch, one copy per distinct axis; layout of the upload: [descriptors][tables]
+    slots, tabs, nints = {}, [], 1                               # (int 0 is a dummy: `tables` is never an empty buffer)
+    for p in params:
+        for insz, outsz in ((p.w, p.new_w), (p.h, p.new_h)):
+            if insz != outsz and (insz, outsz) not in slots:
+                k, b = resize_tables(insz, outsz)
+                slots[(insz, outsz)] = (nints, nints + k.size, k.shape[1])
+                tabs.append((nints, k, b))
+                nints += k.size + b.size
+    off_tab = _align(n * ctypes.sizeof(_GeomDesc))
+    total = off_tab + nints * 4
+    host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    dev = torch.empty(total, dtype=torch.uint8, device=images[0].device)
+    hbuf, dbase = host.numpy(), dev.data_ptr()
+    descs = (_GeomDesc * n).from_buffer(hbuf)
+    ctypes.memset(ctypes.addressof(descs), 0, off_tab)
+    tab = hbuf[off_tab:].view(np.int32)
+    tab[0] = 0
+    for o, k, b in tabs:
+        tab[o: o + k.size] = k.reshape(-1)
+        tab[o + k.size: o + k.size + b.size] = b.reshape(-1)
+    shapes = [(3, p.new_h, p.new_w) if chw_out else (p.new_h, p.new_w, 3) for p in params]
+    if outs is None:
+        outs = [torch.empty(sh, dtype=torch.uint8, device=v.device) for v, sh in zip(images, shapes)]
+    else:
+        outs = list(outs)
+        if len(outs) != n or any(not (o.is_cuda and o.dtype == torch.uint8 and o.is_contiguous() and tuple(o.shape) == sh) for o, sh in zip(outs, shapes)):
+            raise ValueError(f"launch_weak_views: `outs` must be contiguous CUDA uint8 tensors of shapes {shapes}")
+    keep = []                                                    # the two-pass arm's scratch images (stream-ordered: freed after the launches)
+    tiles = hblocks = vblocks = 0
+    fused = ctypes.c_int(0)
+    for i, (v, p, chw) in enumerate(zip(images, params, layouts)):
+        d = descs[i]
+        d.src, d.dst, d.h, d.w, d.new_h, d.new_w = v.data_ptr(), outs[i].data_ptr(), p.h, p.w, p.new_h, p.new_w
+        d.flags = (_GEOM_CHW_IN if chw else 0) | (_GEOM_CHW_OUT if chw_out else 0) | (_GEOM_HFLIP if p.flip else 0)
+        if p.w != p.new_w:
+            d.xk_off, d.xb_off, d.xks = slots[(p.w, p.new_w)]
+        yb = None
+        if p.h != p.new_h:
+            d.yk_off, d.yb_off, d.yks = slots[(p.h, p.new_h)]
+            yb = resize_tables(p.h, p.new_h)[1]
+        L.check(L.lib.aldi_geom_plan(yb.ctypes.data if yb is not None else None, p.h, p.new_h, ctypes.byref(fused)), "aldi_geom_plan")
+        d.tile_begin, d.h_begin, d.v_begin = tiles, hblocks, vblocks
+        if fused.value:
+            d.flags |= _GEOM_FUSED
+            tiles += ((p.new_h + _GEOM_TH - 1) // _GEOM_TH) * ((p.new_w + _GEOM_TW - 1) // _GEOM_TW)
+        else:
+            t = torch.empty(p.h * p.new_w * 3, dtype=torch.uint8, device=v.device)
+            keep.append(t)
+            d.tmp = t.data_ptr()
+            hblocks += (p.h * p.new_w + 255) // 256
+            vblocks += (p.new_h * p.new_w + 255) // 256
+    del descs
+    _upload(dev, host)
+    L.call("aldi_geom_batch_resize", dbase, n, dbase + off_tab, tiles, hblocks, vblocks, ops.stream_ptr())
+    return outs
+
+
+def weak_views(images: Sequence[torch.Tensor], params: Sequence[WeakParams], chw_out: bool = True, stream=None,
+               chw_in=None, outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """Batched weak views: `images` are device uint8 images, (h, w, 3) or (3, h, w), sizes may differ; image i is resized to
+    params[i]'s (new_h, new_w) as Pillow's BILINEAR resize does, byte for byte, and flipped left-right when params[i].flip.
+    Outputs are (3, new_h, new_w) when `chw_out` else (new_h, new_w, 3), on `stream` (default: the current stream)."""
+    if stream is None:
+        return launch_weak_views(images, params, chw_out, chw_in, outs)
+    with torch.cuda.stream(stream):
+        return launch_weak_views(images, params, chw_out, chw_in, outs)
+
+
+def transform_boxes(boxes: np.ndarray, p: WeakParams) -> np.ndarray:
+    """detectron2 `transform_instance_annotations` for XYXY boxes under (ResizeTransform, HFlipTransform), float64 (parity
+    unpinned): corners scaled by new_w / w and new_h / h, flipped as x -> new_w - x, their min / max, clip(min=0), then the
+    minimum with [W, H, W, H]."""
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+    idxs = np.array([(0, 1), (2, 1), (0, 3), (2, 3)]).flatten()
+    coords = b[:, idxs].reshape(-1, 2).copy()
+    coords[:, 0] = coords[:, 0] * (p.new_w * 1.0 / p.w)
+    coords[:, 1] = coords[:, 1] * (p.new_h * 1.0 / p.h)
+    if p.flip:
+        coords[:, 0] = p.new_w - coords[:, 0]
+    coords = coords.reshape(-1, 4, 2)
+    out = np.concatenate((coords.min(axis=1), coords.max(axis=1)), axis=1).clip(min=0)
+    return np.minimum(out, [p.new_w, p.new_h, p.new_w, p.new_h])
+
+
+def transform_instances(inst: dict, p: WeakParams) -> dict:
+    """the record's instances under the weak view: boxes through `transform_boxes`, cast to float32, those with width or
+    height <= 1e-5 dropped with their classes (detectron2 filter_empty_instances), image_size = the new size"""
+    boxes = torch.from_numpy(transform_boxes(inst["gt_boxes"].detach().cpu().numpy(), p)).to(torch.float32)
+    keep = ((boxes[:, 2] - boxes[:, 0]) > 1e-5) & ((boxes[:, 3] - boxes[:, 1]) > 1e-5)
+    out = dict(inst)
+    out["image_size"] = (p.new_h, p.new_w)
+    out["gt_boxes"] = boxes[keep]
+    for key, val in inst.items():
+        if key not in ("gt_boxes", "image_size") and torch.is_tensor(val) and val.dim() >= 1 and val.shape[0] == boxes.shape[0]:
+            out[key] = val[keep]
+    return out

@@ -179,6 +179,15 @@ def add_aldi_config(cfg: CfgNode):
     # the strong views of the training loader from the reference's chain (get_strong_augs of the keys above), built on the
     # device in three launches per batch (aldi_amd/dataloader.py DeviceStrongAugLoader); off: the loader's own views
     _C.AUG.DEVICE_STRONG = False
+    # the weak view's geometry -- detectron2's ResizeShortestEdge (INPUT.MIN_SIZE_TRAIN / MAX_SIZE_TRAIN / MIN_SIZE_TRAIN_SAMPLING) and
+    # horizontal RandomFlip (INPUT.RANDOM_FLIP) of the loader's decoded uint8 image, Pillow-exact -- on the device, in the same loader
+    # stage as the strong chain (aldi_amd/aug.py weak_views); `build_test_loader` then resizes to
+    # INPUT.MIN_SIZE_TEST / MAX_SIZE_TEST.  Off: the loader's images are used at the size they come in
+    _C.AUG.DEVICE_WEAK = False
+    if "MIN_SIZE_TRAIN_SAMPLING" not in _C.INPUT:                 # detectron2 defaults
+        _C.INPUT.MIN_SIZE_TRAIN_SAMPLING = "choice"
+    if "RANDOM_FLIP" not in _C.INPUT:
+        _C.INPUT.RANDOM_FLIP = "horizontal"
     # COCO box AP of `test()` matched and accumulated on the device (aldi_amd/evaluation.py DeviceCOCOEvaluator: the host
     # evaluator's numbers, one device -> host copy per evaluation); off: Detectron2COCOEvaluatorAdapter on the host
     _C.TEST.DEVICE_EVAL = False

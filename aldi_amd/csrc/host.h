@@ -19,7 +19,8 @@ typedef uint16_t bf16_t;  // raw bf16 storage
     X(wgrad_big_group_min, 64) X(wgrad_lds_pad_kb, 0) X(wgrad_f32_tile128, 1) X(wgrad_dma64, 3) X(wgrad_ilv, 0) \
     X(msda_gather, 7) X(msda_gather_list, 1500) X(msda_bin, 1) X(msda_bin_list, 512) X(roialign_sep, 1) X(roialign_bwd_rows, 2) \
     X(colsum_blocks, 256) X(colsum_minrows, 16) X(colsum_nt, 1024) X(colsum_block_kb, 384) \
-    X(stem_mfma, 1) X(stem_pool_wgs, 0) X(sab_blocks, 512) X(ln_bwd_blocks, 512) X(ln_bwd_blocks_narrow, 1024) X(rpn_topk_fused, 1) X(ema_blocks, 2048) X(nms_mask_tri, 1) X(match_wave, 1)
+    X(stem_mfma, 1) X(stem_pool_wgs, 0) X(sab_blocks, 512) X(ln_bwd_blocks, 512) X(ln_bwd_blocks_narrow, 1024) X(rpn_topk_fused, 1) X(ema_blocks, 2048) X(nms_mask_tri, 1) X(match_wave, 1) \
+    X(resize_fused, 1)
 
 struct AldiTuning {
 #define ALDI_KNOB_FIELD(name, dflt) int name;

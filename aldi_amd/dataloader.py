@@ -79,6 +79,14 @@ def device_strong_seed(base: int, rank: int, labeled: bool) -> int:
     return (base * 1000003 + (3000 if labeled else 4000) + 17 * rank) % 2 ** 32
 
 
+def device_weak_seed(base: int, rank: int, labeled: bool) -> int:
+    """the private seed of one rank's labeled / unlabeled WEAK draws (size, flip): a third stream, apart from the strong ones"""
+    return (base * 1000003 + (5000 if labeled else 6000) + 17 * rank) % 2 ** 32
+
+
+RAW_IMG_KEY = "image_raw"
+
+
 class DeviceStrongAugLoader:
     """Wraps a loader that yields lists of dicts carrying `img_weak` (uint8 CHW, host or device) and builds every strong view on
     the device (aldi_amd/aug.py `strong_views`: the reference's chain, three launches per batch).  Each yielded dict is a
@@ -88,10 +96,18 @@ class DeviceStrongAugLoader:
     The draws come from a private RandomState / random.Random seeded with `seed` (as detectron2 seeds each loader worker),
     so the process's global streams are never touched.  It runs one batch ahead: batch k+1's host work (the inner loader,
     the draws) on a background thread, its copies and launches on a side stream, while the caller runs step k; `next()`
-    only makes the caller's current stream wait for the batch (no host sync)."""
+    only makes the caller's current stream wait for the batch (no host sync).
 
-    def __init__(self, loader, augs, seed: int, device=None):
+    `weak` (aldi_amd/aug.py `get_weak_augs`; default None = everything above, unchanged) adds the weak view's geometry to the
+    SAME stage: the record's decoded image -- `image_raw`, uint8 (H, W, 3) or (3, H, W), host or device; absent: `img_weak` --
+    is resized and flipped on the device (`launch_weak_views`) into `img_weak`, (3, new_h, new_w), on the same side stream
+    and ahead of the strong launches, which then work on it.  The size and flip draws come from a third private RandomState
+    seeded with `weak_seed`; `instances` are transformed on the host (`transform_instances`), `height` / `width` keep the
+    raw size.  The background thread still does host work only: every launch is issued by the caller's thread."""
+
+    def __init__(self, loader, augs, seed: int, device=None, weak=None, weak_seed=None):
         self.loader, self.augs, self.seed, self.device = loader, augs, int(seed), device
+        self.weak, self.weak_seed = weak, int(seed if weak_seed is None else weak_seed)
 
     def __iter__(self):
         return _DeviceStrongAugIter(self)
@@ -102,6 +118,8 @@ class _DeviceStrongAugIter:
         self.it = iter(owner.loader)
         self.augs = owner.augs
         self.np_rng, self.py_rng = np.random.RandomState(owner.seed), random.Random(owner.seed)
+        self.weak = owner.weak
+        self.weak_rng = np.random.RandomState(owner.weak_seed) if owner.weak is not None else None
         self.device = torch.device(owner.device) if owner.device is not None else torch.device("cuda", torch.cuda.current_device())
         self.side = torch.cuda.Stream(self.device)
         self.pool = ThreadPoolExecutor(1)
@@ -112,6 +130,8 @@ class _DeviceStrongAugIter:
         """host work (background thread): the inner loader's batch, pinned weak views, the draws in image order"""
         from . import aug
         batch = next(self.it)
+        if self.weak is not None:
+            return self._prepare_weak(batch)
         weak, params = [], []
         for rec in batch:
             w = rec[WEAK_IMG_KEY]
@@ -122,14 +142,52 @@ class _DeviceStrongAugIter:
                 params.append(aug.draw_strong_params(self.augs, int(w.shape[1]), int(w.shape[2]), np_rng=self.np_rng, py_rng=self.py_rng))
         return batch, weak, params
 
+    def _prepare_weak(self, batch):
+        """host work with the weak stage on: the size / flip draws, the (cached) resize tables, the pinned raw images, the
+        transformed instances, then the strong draws for the NEW sizes"""
+        from . import aug
+        raws, wparams, params, out = [], [], [], []
+        for rec in batch:
+            raw = rec.get(RAW_IMG_KEY, rec.get(WEAK_IMG_KEY))
+            if raw is None or raw.dtype != torch.uint8 or raw.dim() != 3 or 3 not in (raw.shape[0], raw.shape[2]):
+                raise ValueError(f"DeviceStrongAugLoader: `{RAW_IMG_KEY}` (or `{WEAK_IMG_KEY}`) must be a uint8 (H, W, 3) or (3, H, W) image")
+            chw = RAW_IMG_KEY not in rec or raw.shape[2] != 3          # (`img_weak` is CHW by contract; an (H, W, 3) raw image is HWC)
+            h, w = (int(raw.shape[1]), int(raw.shape[2])) if chw else (int(raw.shape[0]), int(raw.shape[1]))
+            wp = aug.draw_weak_params(self.weak, h, w, self.weak_rng)
+            for insz, outsz in ((wp.w, wp.new_w), (wp.h, wp.new_h)):
+                if insz != outsz:
+                    aug.resize_tables(insz, outsz)
+            raws.append((raw.contiguous() if raw.is_cuda else raw.contiguous().pin_memory(), chw))
+            wparams.append(wp)
+            rec = dict(rec)
+            rec.pop(RAW_IMG_KEY, None)
+            if rec.get("instances") is not None:
+                rec["instances"] = aug.transform_instances(rec["instances"], wp)
+            rec.setdefault("height", h)
+            rec.setdefault("width", w)
+            out.append(rec)
+            if self.augs is not None:
+                params.append(aug.draw_strong_params(self.augs, wp.new_h, wp.new_w, np_rng=self.np_rng, py_rng=self.py_rng))
+        return out, (raws, wparams), params
+
     def _issue(self, prepared):
         """device work (caller's thread): weak-view copies and the batch's launches on the side stream"""
         from . import aug
         batch, weak, params = prepared
+        raws = None
+        if self.weak is not None:
+            raws, wparams = weak
+            weak = [r for r, _ in raws]
         if any(w.is_cuda for w in weak):
             self.side.wait_stream(torch.cuda.current_stream(self.device))       # device weak views come from the caller's stream
         with torch.cuda.device(self.device), torch.cuda.stream(self.side):
             dweak = [w if w.is_cuda else w.to(self.device, non_blocking=True) for w in weak]
+            if raws is not None:                                                # H2D copy -> resize + flip -> (below) the strong launches
+                draw = dweak
+                dweak = aug.launch_weak_views(draw, wparams, chw_out=True, chw_in=[chw for _, chw in raws])
+                for t, (r, _) in zip(draw, raws):
+                    if r.is_cuda:                                               # a caller's device image: the side stream is its last user
+                        t.record_stream(self.side)
             strong = aug.launch_strong_views(dweak, params, chw=True) if self.augs is not None else dweak
             ev = torch.cuda.Event()
             ev.record(self.side)

@@ -19,7 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import synthetic
-from .dataloader import DeviceStrongAugLoader, SyntheticDetectionLoader, WeakStrongDataloader, device_strong_seed
+from .dataloader import DeviceStrongAugLoader, SyntheticDetectionLoader, WeakStrongDataloader, device_strong_seed, device_weak_seed
 from .distill import build_distiller
 from .ema import EMA
 from .model import build_aldi
@@ -860,17 +860,24 @@ class ALDITrainer(DefaultTrainer):
         fixed = bool(syn.get("FIXED", False))
         labeled_loader = SyntheticDetectionLoader(labeled_bs // world, h, w, K, 1000 + 17 * rank, True, fixed=fixed) if labeled_bs > 0 else None
         unlabeled_loader = SyntheticDetectionLoader(unlabeled_bs // world, h, w, K, 2000 + 17 * rank, False, fixed=fixed) if unlabeled_bs > 0 else None
-        if cfg.AUG.get("DEVICE_STRONG", False):
+        device_strong, device_weak = bool(cfg.AUG.get("DEVICE_STRONG", False)), bool(cfg.AUG.get("DEVICE_WEAK", False))
+        if device_strong or device_weak:
             # strong views from the reference's chain on the device (aldi/trainer.py:224-236 include_strong_augs: only for a
-            # domain whose strong view the batch asks for), private draws seeded per rank and domain
-            from .aug import get_strong_augs
+            # domain whose strong view the batch asks for), private draws seeded per rank and domain.  AUG.DEVICE_WEAK puts the
+            # weak view's geometry (ResizeShortestEdge + RandomFlip of the loader's decoded image, aldi/aug.py:16-37) into the
+            # same stage, ahead of the strong chain, with draws of its own
+            from .aug import get_strong_augs, get_weak_augs
             base = max(int(cfg.SEED), 0)
+            weak = get_weak_augs(cfg, True) if device_weak else None
+
+            def stage(loader, labeled, part):
+                return DeviceStrongAugLoader(loader, get_strong_augs(cfg, labeled) if device_strong and part in contents else None,
+                                             device_strong_seed(base, rank, labeled), weak=weak,
+                                             weak_seed=device_weak_seed(base, rank, labeled) if device_weak else None)
             if labeled_loader is not None:
-                labeled_loader = DeviceStrongAugLoader(labeled_loader, get_strong_augs(cfg, True) if "labeled_strong" in contents else None,
-                                                       device_strong_seed(base, rank, True))
+                labeled_loader = stage(labeled_loader, True, "labeled_strong")
             if unlabeled_loader is not None:
-                unlabeled_loader = DeviceStrongAugLoader(unlabeled_loader, get_strong_augs(cfg, False) if "unlabeled_strong" in contents else None,
-                                                         device_strong_seed(base, rank, False))
+                unlabeled_loader = stage(unlabeled_loader, False, "unlabeled_strong")
         return WeakStrongDataloader(labeled_loader, unlabeled_loader, batch_contents)
 
     def before_step(self):
@@ -893,8 +900,18 @@ class ALDITrainer(DefaultTrainer):
         n, K = int(syn_.get("VAL_IMAGES", 8)), _num_classes(cfg)
         g = torch.Generator().manual_seed(4242)
         batches, records = [], []
+        weak = None
+        if cfg.AUG.get("DEVICE_WEAK", False):
+            # detectron2's test-time mapper: ResizeShortestEdge at MIN_SIZE_TEST / MAX_SIZE_TEST, no flip and nothing drawn; the
+            # records keep the raw height / width, so the evaluators' rescaling brings the detections back
+            from . import aug
+            weak = aug.get_weak_augs(cfg, False)[0]
+            size = weak.short_edge_length[0]
         for i in range(n):
             img, inst = synthetic.make_image(h, w, int(torch.randint(5, 21, (1,), generator=g)), K, g)
+            if weak is not None and size != 0:
+                nh, nw = weak.get_output_shape(h, w, size, weak.max_size)
+                img = aug.weak_views([img.to(cfg.MODEL.DEVICE).contiguous()], [aug.WeakParams(h, w, nh, nw, False)], chw_out=True, chw_in=True)[0]
             batches.append([{"image": img, "image_id": i, "height": h, "width": w}])
             records.append(dict(image_id=i, height=h, width=w,
                                 annotations=[dict(bbox=b.tolist(), bbox_mode="XYXY_ABS", category_id=int(c))

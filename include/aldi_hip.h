@@ -105,6 +105,8 @@ int aldi_noop(aldi_stream_t stream);
  *   stem_mfma            1 = MFMA stem kernel in bf16 mode
  *   stem_pool_wgs        workgroups of the persistent stem + pool kernel (0 = two per compute unit, the default; never more than tiles)
  *   sab_blocks, ln_bwd_blocks, ln_bwd_blocks_narrow   ConvNeXt scale-and-bias / LayerNorm backward launch geometry
+ *   resize_fused         1 = aldi_geom_plan lets an image whose row windows fit the LDS budget take the fused resize kernel; 0 = every image
+ *                        through the two-pass arm (same bytes)
  * aldi_last_dispatch(): name of the kernel variant chosen by the most recent aldi_conv_igemm / aldi_conv_wgrad call on
  * this thread, e.g. "igemm<bf16,256,128,4,2,flat,halo>" or "wgrad_bf16_big splits=4" (valid until the next call). */
 int aldi_set_tuning(const char* name, int value);
@@ -626,6 +628,35 @@ int aldi_aug_batch_view(const aldi_aug_desc* desc, int n, int ntiles, const unsi
  * takes two); the state at outputs 0, seg, 2 seg, ... < n goes to snaps[k][624] / snap_pos[k] (at most max_snaps; seg <= 0:
  * none).  Equals get_state() after rand(n / 2) bit for bit. */
 int aldi_np_mt_advance(unsigned int* key, int* pos, long n, long seg, unsigned int* snaps, int* snap_pos, long max_snaps);
+
+/* ---------------------------------------------------------------------------------------
+ * Weak-view geometry on the device: detectron2's ResizeShortestEdge + horizontal RandomFlip of a uint8
+ * image = Pillow's Image.resize(BILINEAR) (fixed point, horizontal pass rounded to uint8, then the vertical pass) and an index
+ * reversal at the store.  The host builds the per-axis tables in Pillow's double arithmetic (aldi_amd/aug.py resize_tables):
+ * for an axis insz -> outsz, coefficients int k[outsz][ksize] (22 fractional bits, zero past the tap count) and bounds
+ * int b[outsz][2] = (first input index, tap count); out = clip(((1 << 21) + sum_t in[first + t] * k[t]) >> 22, 0, 255).
+ * Bit-identical to Pillow.
+ * --------------------------------------------------------------------------------------- */
+enum { ALDI_GEOM_CHW_IN = 1, ALDI_GEOM_CHW_OUT = 2, ALDI_GEOM_HFLIP = 4, ALDI_GEOM_FUSED = 8 };
+enum { ALDI_GEOM_TH = 16, ALDI_GEOM_TW = 64,      /* output tile of the fused kernel */
+       ALDI_GEOM_LDS_ROWS = 96 };                 /* input rows one tile may stage in LDS (x 64 pixels x 3 bytes = 18 KiB) */
+typedef struct aldi_geom_desc {
+    const unsigned char* src;                     /* device, uint8 HWC or CHW (flag CHW_IN), contiguous, h x w */
+    unsigned char* dst;                           /* device, HWC or CHW (flag CHW_OUT), new_h x new_w */
+    unsigned char* tmp;                           /* two-pass arm: h x new_w x 3 bytes of scratch; NULL with flag FUSED */
+    int h, w, new_h, new_w;
+    int flags;                                    /* CHW_IN, CHW_OUT, HFLIP (x -> new_w - 1 - x at the store), FUSED (the arm, from aldi_geom_plan) */
+    int xk_off, xb_off, xks;                      /* x tables: offsets in ints into `tables`, ksize; xks 0 = width kept, no horizontal pass */
+    int yk_off, yb_off, yks;                      /* y tables, likewise */
+    int tile_begin;                               /* first tile in the fused launch's grid (16 x 64 output tiles; no tiles unless FUSED) */
+    int h_begin, v_begin;                         /* first block in the two-pass launches' grids (256 pixels per block; none with FUSED) */
+} aldi_geom_desc;
+/* Host only: *fused = 1 when tuning knob resize_fused is on and every 16-row output tile's input row window, read from the
+ * y bounds [new_h][2] (ignored when h == new_h), fits ALDI_GEOM_LDS_ROWS. */
+int aldi_geom_plan(const int* ybounds, int h, int new_h, int* fused);
+/* N images in at most three launches: the fused kernel over ntiles tiles, then the two-pass arm's horizontal (nh_blocks) and
+ * vertical (nv_blocks) launches for the images without flag FUSED.  desc and tables are device pointers. */
+int aldi_geom_batch_resize(const aldi_geom_desc* desc, int n, const int* tables, int ntiles, int nh_blocks, int nv_blocks, aldi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * COCO box-AP evaluation (aldi_amd/evaluation.py DeviceCOCOEvaluator, `TEST.DEVICE_EVAL`): pycocotools' COCOeval for
