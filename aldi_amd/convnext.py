@@ -348,7 +348,7 @@ class ConvNeXtRCNN(_engine_base()):
         ops.subsample2_bwd(gP[4], gP[3])
         for l in range(4):
             ops.add_f32(gP[l], gP_roi[l], gP[l])
-        cb = getattr(self, "grad_ready", None)
+        cb = self.grad_ready
         if cb is not None:
             cb(vp.ranges([n for n in vp.spec if n.startswith(("proposal_generator.", "roi_heads."))]))
         # FPN

@@ -393,26 +393,58 @@ class Ctx(dict):
     __setattr__ = dict.__setitem__
 
 
+def _knob(env: str, default, doc: str):
+    return dataclasses.field(default=default, metadata=dict(env=env, doc=doc))
+
+
+@dataclasses.dataclass(frozen=True)
+class EngineKnobs:
+    """every environment switch of the engine, read ONCE (when the engine is built): a switch means the same thing in the eager warm-up and
+    inside a captured graph.  bool: "1" is on, anything else off; DESIGN.md section 30 lists them from this table."""
+    fused_stem: bool = _knob("ALDI_FUSED_STEM", True, "bf16: stem conv + max-pool in one kernel")
+    fused_res2: bool = _knob("ALDI_FUSED_RES2", True, "bf16: a res2 bottleneck (no saved activations) in one kernel")
+    fused_res2_shortcut: bool = _knob("ALDI_FUSED_RES2_SHORTCUT", True, "... and res2.0's shortcut conv inside that kernel")
+    fused_stage_entrance: bool = _knob("ALDI_FUSED_STAGE_ENTRANCE", True, "bf16: the shortcut of res3.0 / res4.0 / res5.0 inside conv3's launch, its gradient on the compact grid (section 21)")
+    level_groups: bool = _knob("ALDI_LEVEL_GROUPS", True, "one launch for a layer applied to several pyramid levels")
+    mask_bits: bool = _knob("ALDI_MASK_BITS", True, "ReLU masks of the block outputs as bits for the backward")
+    mask_bits_inner: bool = _knob("ALDI_MASK_BITS_INNER", True, "... and of the two inner maps of every bottleneck")
+    mask_bits_fc: bool = _knob("ALDI_MASK_BITS_FC", True, "... and of the box head's FC2")
+    roi_prepare_fused: bool = _knob("ALDI_ROI_PREPARE_FUSED", True, "append GT, match, classes and the fg / bg lists in one launch instead of eight")
+    box_loss_fused: bool = _knob("ALDI_BOX_LOSS_FUSED", True, "the box head's losses of all chunks (+ RoI distillation) as one launch")
+    sparse_rpn_backward: bool = _knob("ALDI_RPN_SPARSE_BWD", True, "the RPN head's backward over the sampled anchors' pixels only (0: the dense convolutions)")
+    upsample_chain: bool = _knob("ALDI_UPSAMPLE_CHAIN", True, "the FPN's three top-down gradient sums in one launch (where every level halves exactly)")
+    aux_stream: bool = _knob("ALDI_AUX_STREAM", True, "an auxiliary stream for the RPN-side losses and the sparse RPN backward's gather")
+    wgrad_stream: bool = _knob("ALDI_WGRAD_STREAM", True, "the weight gradients on a second stream beside the data-gradient chain")
+    wgrad_prio: int = _knob("ALDI_WGRAD_PRIO", 0, "priority of that stream")
+    group_wgrad: bool = _knob("ALDI_WGRAD_GROUP", True, "bf16: a layer group's weight gradients in one launch")
+    wgrad_tail_split: int = _knob("ALDI_WGRAD_TAIL_SPLIT", 2, "res3's weight-gradient group launched every this many blocks (0: once)")
+    wgrad_subsample: bool = _knob("ALDI_WGRAD_SUBSAMPLE", True, "bf16, grouped: the input of a stride-2 1x1 conv gathered once, its weight gradient joins the group")
+    wgrad_subsample_side: bool = _knob("ALDI_WGRAD_SUBSAMPLE_SIDE", True, "... gathered on the weight-gradient stream")
+    wgrad_bias_fused: bool = _knob("ALDI_WGRAD_BIAS_FUSED", True, "bf16, grouped: the bias gradient inside the weight-gradient launch (0: column-sum launches)")
+
+    @classmethod
+    def from_env(cls, env=None) -> "EngineKnobs":
+        """env = the mapping to read (the process environment)"""
+        env = os.environ if env is None else env
+        raw = {f: env.get(f.metadata["env"]) for f in dataclasses.fields(cls)}
+        return cls(**{f.name: v == "1" if isinstance(f.default, bool) else int(v) for f, v in raw.items() if v is not None})
+
+
 class RCNN:
     p = D2Params()          # (subclasses that do not go through this constructor run on detectron2's defaults)
     # events.HeadStatSink | None: with a sink attached (SOLVER.LOG_PERIOD > 0) the launches that produce a micro-step's loss VALUES are
     # followed by aldi_rpn_label_counts / aldi_box_cls_stats on the same stream with the same inputs; None: the launch sequence has neither
     stats_sink = None
 
-    def __init__(self, weights: Weights, num_classes: int, params: Optional[D2Params] = None):
+    def __init__(self, weights: Weights, num_classes: int, params: Optional[D2Params] = None, knobs: Optional[EngineKnobs] = None):
         self.wts = weights
         if params is not None:
             self.p = params
         self.K = num_classes
-        self.device, self.dtype = weights.device, weights.dtype
+        self.dtype = weights.dtype
         self.Cp = weights.layout.t["box_pred"].rows
         self.Ch = weights.layout.t["rpn_head_out"].rows
-        self._anchor_cache: Dict[tuple, tuple] = {}
-        self._ws: Dict[str, torch.Tensor] = {}
-        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
-        # the host only runs tiny torch-CPU ops (RNG draws, index packing); on a many-core host the default
-        # intra-op thread pool makes torch.randperm(268k) ~20x slower than one thread
-        torch.set_num_threads(1)
+        self._init_common(weights.device, knobs)
         # discriminator layers in nn.Sequential order (hidden convs / linears, the last entry is the 1-logit Linear) and the FPN
         # level the image-level one reads (aldi/align.py:22-52)
         idx = lambda n: int(n.rsplit(".", 1)[1])
@@ -420,20 +452,35 @@ class RCNN:
         self.img_da_layers = sorted((n for n in names if n.startswith("img_align.model.")), key=idx)
         self.ins_da_layers = sorted((n for n in names if n.startswith("ins_align.model.")), key=idx)
         self.has_img_da, self.has_ins_da = bool(self.img_da_layers), bool(self.ins_da_layers)
-        self.fused_stem = os.environ.get("ALDI_FUSED_STEM", "1") == "1"                  # bf16: stem conv + max-pool in one kernel
-        self.wgrad_tail_split = int(os.environ.get("ALDI_WGRAD_TAIL_SPLIT", "2"))       # res3's weight-gradient group launched every this many blocks (0: once)
-        self.group_wgrad = os.environ.get("ALDI_WGRAD_GROUP", "1") == "1"                # bf16: a layer group's weight gradients in one launch
-        self.mask_bits = os.environ.get("ALDI_MASK_BITS", "1") == "1"                    # ReLU masks of the block outputs as bits for the backward
-        self.mask_bits_inner = os.environ.get("ALDI_MASK_BITS_INNER", "1") == "1"        # ... and of the two inner maps of every bottleneck
-        self.level_groups = os.environ.get("ALDI_LEVEL_GROUPS", "1") == "1"              # one launch for a layer applied to several pyramid levels
-        self.fused_res2 = os.environ.get("ALDI_FUSED_RES2", "1") == "1"                  # bf16: a res2 bottleneck (no saved activations) in one kernel
-        self.fused_res2_shortcut = os.environ.get("ALDI_FUSED_RES2_SHORTCUT", "1") == "1"  # ... and res2.0's shortcut conv inside that kernel
-        # bf16: the projection shortcut of res3.0 / res4.0 / res5.0 inside the block's conv3 launch (csrc/igemm_pair.h; same bits)
-        self.fused_stage_entrance = os.environ.get("ALDI_FUSED_STAGE_ENTRANCE", "1") == "1"
-        self._wg_queue: list = []
-        self.sparse_rpn_backward = os.environ.get("ALDI_RPN_SPARSE_BWD", "1") == "1"      # tests flip the attribute to compare with the dense form
         spec = getattr(weights.layout, "img_da", None)
         self.img_da_level = ("p2", "p3", "p4", "p5", "p6").index(spec["layer"]) if spec else 0
+
+    def _init_common(self, device, knobs: Optional[EngineKnobs] = None):
+        """the state every engine has, whatever its parameter container (the two side streams: see `_wgrad_stream` / `_aux_stream`)"""
+        self.device = device
+        self.knobs = knobs or EngineKnobs.from_env()
+        self._anchor_cache: Dict[tuple, tuple] = {}
+        self._ws: Dict[str, torch.Tensor] = {}
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        # the host only runs tiny torch-CPU ops (RNG draws, index packing); on a many-core host the default
+        # intra-op thread pool makes torch.randperm(268k) ~20x slower than one thread
+        torch.set_num_threads(1)
+        self._wg_queue: list = []            # weight gradients queued for the next grouped launch (`_wgrad` / `_flush_wgrads`)
+        self._wgrad_pending = False          # the weight-gradient stream holds work the main stream has not joined
+        self._sub_cache: dict = {}           # id(x) -> (x, its stride-2 gather): conv1 and the shortcut of a stage entrance share it
+        self.grad_ready = None               # callback(ranges[, events]) of an attached gradient exchange / in-step optimizer
+
+    sparse_rpn_backward = property(lambda self: self.knobs.sparse_rpn_backward)       # (read-only: the benchmark's throughput model reads it)
+
+    @contextlib.contextmanager
+    def with_knobs(self, **changes):
+        """run the body with these switches changed, then put the old table back"""
+        old = self.knobs
+        self.knobs = dataclasses.replace(old, **changes)
+        try:
+            yield self
+        finally:
+            self.knobs = old
 
     # ------------------------------------------------------------------ inputs
     def stage_images(self, images: Sequence[torch.Tensor]):
@@ -545,57 +592,35 @@ class RCNN:
         streams = (stream_a, stream_b): no grouping -- each model's launches go to its own stream, ISSUED alternately (a hipGraph
         hands its nodes to the queues in capture order: a branch captured after the other one starts when the host has submitted
         everything before it, 2 ms into the phase for the teacher's pass behind the student's trunk)"""
-        res = [None, None]
-        ctx_a = torch.cuda.stream(streams[0]) if streams else contextlib.nullcontext()
-        ctx_b = torch.cuda.stream(streams[1]) if streams else contextlib.nullcontext()
-        try:
-            with ctx_a:
-                ra = next(gen_a)
-        except StopIteration as e:
-            ra, res[0] = None, e.value
-        try:
-            with ctx_b:
-                rb = next(gen_b)
-        except StopIteration as e:
-            rb, res[1] = None, e.value
-        while ra is not None or rb is not None:
+        engs, gens = (eng_a, eng_b), (gen_a, gen_b)
+        ctxs = [torch.cuda.stream(s) for s in streams] if streams else [contextlib.nullcontext()] * 2
+
+        def _advance(gen, value, first=False):
+            """-> (the generator's next request, None), or (None, its return value) once it has returned"""
+            try:
+                return (next(gen) if first else gen.send(value)), None
+            except StopIteration as e:
+                return None, e.value
+        req, res = [None, None], [None, None]
+        for i in (0, 1):
+            with ctxs[i]:
+                req[i], res[i] = _advance(gens[i], None, first=True)
+        while req[0] is not None or req[1] is not None:
+            live = [i for i in (0, 1) if req[i] is not None]
             if streams:
-                if ra is not None:
-                    with ctx_a:
-                        ya = eng_a._serve(ra)
-                        try:
-                            ra = gen_a.send(ya)
-                        except StopIteration as e:
-                            ra, res[0] = None, e.value
-                if rb is not None:
-                    with ctx_b:
-                        yb = eng_b._serve(rb)
-                        try:
-                            rb = gen_b.send(yb)
-                        except StopIteration as e:
-                            rb, res[1] = None, e.value
+                for i in live:
+                    with ctxs[i]:
+                        req[i], res[i] = _advance(gens[i], engs[i]._serve(req[i]))
                 continue
-            paired = any(not isinstance(r, list) and r[2].get("pre") is not None for r in (ra, rb) if r is not None)     # (a pair launch has no group form)
-            if ra is not None and rb is not None and not paired:
-                la, lb = (ra if isinstance(ra, list) else [ra]), (rb if isinstance(rb, list) else [rb])
+            paired = any(not isinstance(req[i], list) and req[i][2].get("pre") is not None for i in live)     # (a pair launch has no group form)
+            if len(live) == 2 and not paired:
+                la, lb = [r if isinstance(r, list) else [r] for r in req]
                 ys = ops.conv2d_group([eng_a._conv_call(r[0], r[1], **r[2]) for r in la] + [eng_b._conv_call(r[0], r[1], **r[2]) for r in lb])
-                ya = ys[:len(la)] if isinstance(ra, list) else ys[0]
-                yb = ys[len(la):] if isinstance(rb, list) else ys[len(la)]
+                ys = [ys[:len(la)] if isinstance(req[0], list) else ys[0], ys[len(la):] if isinstance(req[1], list) else ys[len(la)]]
             else:
-                if ra is not None:
-                    ya = eng_a._serve(ra)
-                if rb is not None:
-                    yb = eng_b._serve(rb)
-            if ra is not None:
-                try:
-                    ra = gen_a.send(ya)
-                except StopIteration as e:
-                    ra, res[0] = None, e.value
-            if rb is not None:
-                try:
-                    rb = gen_b.send(yb)
-                except StopIteration as e:
-                    rb, res[1] = None, e.value
+                ys = [engs[i]._serve(req[i]) if i in live else None for i in (0, 1)]
+            for i in live:
+                req[i], res[i] = _advance(gens[i], ys[i])
         return res[0], res[1]
 
     def trunk(self, st_u8: torch.Tensor, sizes, save: bool) -> Ctx:
@@ -605,7 +630,7 @@ class RCNN:
     def prefix_pipelinable(self) -> bool:
         """stem + res2 are frozen (FREEZE_AT = 2: nothing of them is saved for the backward and no update touches their weights) and run as the
         fused bf16 kernels: their forward for batch k + 1 may run while step k still computes (fused_step: cross-step pipelining)"""
-        return type(self) is RCNN and self.dtype == torch.bfloat16 and self.fused_stem and self.fused_res2
+        return type(self) is RCNN and self.dtype == torch.bfloat16 and self.knobs.fused_stem and self.knobs.fused_res2
 
     def trunk_steps(self, st_u8: torch.Tensor, sizes, save: bool, fpn: bool = True, pre: Optional[torch.Tensor] = None,
                     prefix_out: Optional[torch.Tensor] = None):
@@ -616,7 +641,7 @@ class RCNN:
         bu = "backbone.bottom_up."
         if pre is not None:
             x = pre
-        elif self.dtype == torch.bfloat16 and self.fused_stem:
+        elif self.dtype == torch.bfloat16 and self.knobs.fused_stem:
             x = ops.stem_pool_forward(st_u8, sizes, W.stem_packed(bu + "stem.conv1"), W.scale(bu + "stem.conv1"), W.shift(bu + "stem.conv1"),
                                       self.p.pixel_mean, self.p.pixel_std)
         else:
@@ -629,7 +654,7 @@ class RCNN:
         out_bits = {}                          # data_ptr of a saved block output -> its ReLU bit mask
         # res2 keeps nothing for the backward (FREEZE_AT = 2; `blocks` below starts at res3): each of its bottlenecks is ONE kernel
         # whose two 64-channel intermediate maps stay in the LDS (csrc/bneck.hip)
-        fuse2 = self.dtype == torch.bfloat16 and self.fused_res2
+        fuse2 = self.dtype == torch.bfloat16 and self.knobs.fused_res2
         if fuse2:
             res2 = [f"{bu}res2.{b}.conv{k}" for b in range(STAGE_BLOCKS[0]) for k in (1, 2, 3)]
             fw = dict(zip(res2, W.folded(res2)))
@@ -643,19 +668,19 @@ class RCNN:
                 if si == 0 and fuse2:
                     # res2.0's projection shortcut is formed inside the block's kernel from the x tile it already holds (no launch, no 256-channel
                     # map through memory); res = x there: not read
-                    fold_sc = b == 0 and self.fused_res2_shortcut
+                    fold_sc = b == 0 and self.knobs.fused_res2_shortcut
                     sc = (yield x, p + "shortcut", {}) if b == 0 and not fold_sc else x
                     x = ops.bottleneck_fused(x, sc, fw[p + "conv1"], fw[p + "conv2"], fw[p + "conv3"], W.shift(p + "conv1"), W.shift(p + "conv2"),
                                              W.shift(p + "conv3"), out=prefix_out if (prefix_out is not None and b == nb - 1) else None,
                                              shortcut=(W.w(p + "shortcut"), W.scale(p + "shortcut"), W.shift(p + "shortcut")) if fold_sc else None)
                     continue
                 # a stage's first block: the projection shortcut is formed inside conv3's launch (no launch and no [N][Ho][Wo][4 * mid] map of its own)
-                fold_sc = b == 0 and self.dtype == torch.bfloat16 and self.fused_stage_entrance
+                fold_sc = b == 0 and self.dtype == torch.bfloat16 and self.knobs.fused_stage_entrance
                 sc = (yield x, p + "shortcut", {}) if b == 0 and not fold_sc else x
                 # every saved ReLU output's mask as BITS beside it (1/16 of the tensor): what the data-gradient launch that needs the mask -- the
                 # next block's conv1 / the lateral conv for a block output, conv3's / conv2's for the two inner maps -- multiplies by instead of
                 # reading the whole activation again for its sign; with bits those launches also take the direct epilogue (csrc/igemm.hip)
-                want_bits = save and si > 0 and self.mask_bits and self.dtype == torch.bfloat16
+                want_bits = save and si > 0 and self.knobs.mask_bits and self.dtype == torch.bfloat16
 
                 def bits_for(inp, name):
                     if not want_bits:
@@ -664,9 +689,9 @@ class RCNN:
                     ho = (inp.shape[1] + 2 * lt.pad - lt.kk) // lt.stride + 1
                     wo = (inp.shape[2] + 2 * lt.pad - lt.kk) // lt.stride + 1
                     return torch.empty(inp.shape[0] * ho * wo * (lt.wshape[0] // 8), dtype=torch.uint8, device=self.device)
-                b1 = bits_for(x, p + "conv1") if self.mask_bits_inner else None
+                b1 = bits_for(x, p + "conv1") if self.knobs.mask_bits_inner else None
                 h1 = yield x, p + "conv1", dict(relu=True, bits_out=b1)
-                b2 = bits_for(h1, p + "conv2") if self.mask_bits_inner else None
+                b2 = bits_for(h1, p + "conv2") if self.knobs.mask_bits_inner else None
                 h2 = yield h1, p + "conv2", dict(relu=True, bits_out=b2)
                 bits = bits_for(h2, p + "conv3")
                 if fold_sc:
@@ -692,7 +717,7 @@ class RCNN:
         prev = {}
         P = {}
         prev[5] = yield cs[3], "backbone.fpn_lateral5", {}
-        if self.level_groups:
+        if self.knobs.level_groups:
             # the top-down sums first, then the four output convs (256 -> 256, 3x3, on 268800 / 67200 / 16800 / 4200 pixels at N = 4)
             # as ONE launch: alone, the p4 / p5 ones are a fraction of a round of workgroups each
             for lvl in (4, 3, 2):
@@ -724,7 +749,7 @@ class RCNN:
             view = flat[0, o:o + n, 0].view(f.shape[0], f.shape[1], f.shape[2], FPN_C)
             reqs.append((f, "proposal_generator.rpn_head.conv", dict(relu=True, out=view)))
             o += n
-        if self.level_groups:
+        if self.knobs.level_groups:
             ts = yield reqs             # the shared 3x3 conv on the five levels: one launch
         else:
             for r in reqs:
@@ -745,7 +770,7 @@ class RCNN:
         # FC2's ReLU mask as bits for the predictors' data gradient (1/16 of the bytes, and that launch takes the direct epilogue); FC1 is a
         # split-K launch whose second pass does not write bits: its mask stays the activation itself
         bits2 = None
-        if c is not None and self.mask_bits and self.dtype == torch.bfloat16 and R > 0 and os.environ.get("ALDI_MASK_BITS_FC", "1") == "1":
+        if c is not None and self.knobs.mask_bits and self.dtype == torch.bfloat16 and R > 0 and self.knobs.mask_bits_fc:
             bits2 = torch.empty(R * (FC_DIM // 8), dtype=torch.uint8, device=self.device)
         fc2 = self.conv(fc1, "roi_heads.box_head.fc2", relu=True, bits_out=bits2)
         pred = self.conv(fc2, "box_pred", want_f32=True).view(R, self.Cp)
@@ -976,7 +1001,7 @@ class RCNN:
         gt = c.gt
         align_list = []
         # the box head's losses of all chunks (+ RoI distillation + the compute-dtype copy of the gradient rows) as ONE launch: csrc/roi.hip
-        box_fused = [] if (c.R > 0 and len(c.chunks) <= 8 and self.Cp % 2 == 0 and os.environ.get("ALDI_BOX_LOSS_FUSED", "1") == "1") else None
+        box_fused = [] if (c.R > 0 and len(c.chunks) <= 8 and self.Cp % 2 == 0 and self.knobs.box_loss_fused) else None
         c.gpred_lo = None
         sink, stat_rows = self.stats_sink, []
         for ci, (ch, sc_) in enumerate(zip(c.chunks, scales)):
@@ -1095,7 +1120,7 @@ class RCNN:
         labels = torch.empty((N, Lc), dtype=torch.int32, device=dev)
         cls = torch.empty((N, Lc), dtype=torch.int32, device=dev)
         lists = torch.empty((N, 2, Lc), dtype=torch.int32, device=dev)
-        fused = os.environ.get("ALDI_ROI_PREPARE_FUSED", "1") == "1" and GMAX <= 256
+        fused = self.knobs.roi_prepare_fused and GMAX <= 256
         # tail = (word_a, word_b): two device words the fused launch appends to the counts (the fused step's error words: one copy to the host)
         cbuf = torch.empty((2 * N + 2,), dtype=torch.int32, device=dev) if (tail is not None and fused) else None
         counts = cbuf[: 2 * N].view(N, 2) if cbuf is not None else torch.empty((N, 2), dtype=torch.int32, device=dev)
@@ -1230,9 +1255,7 @@ class RCNN:
 
     def _backward_trunk(self, c: Ctx, align_list: List[dict]):
         """heads -> FPN -> res5..res3 given d(loss)/d(head outputs) in c.ghead / c.gpred (fp32)."""
-        W = self.wts
-        T = self.dtype
-        dev = self.device
+        W, T, dev = self.wts, self.dtype, self.device
         # The stride-2 stages scatter their input gradient into every other pixel of a zero map (res5 -> c4, res4 -> c3): clear
         # those maps NOW on the side stream, beside the box head's backward, instead of in the middle of the data-gradient chain
         gx_pre, gx_ev = {}, None
@@ -1247,7 +1270,7 @@ class RCNN:
         # The sparse RPN-head backward up to its scatter needs the head gradients only: on an auxiliary stream, beside the box head's
         # backward and ROIAlign's (it was ~0.12 ms of small launches between ROIAlign's backward and the FPN's)
         sp_pre, aux = None, None
-        if self.sparse_rpn_backward:
+        if self.knobs.sparse_rpn_backward:
             aux = self._aux_stream()
             if aux is not None:
                 aux.wait_stream(torch.cuda.current_stream())
@@ -1257,7 +1280,7 @@ class RCNN:
         # ROIAlign's share of d(loss)/d(P_l).  With the sparse RPN-head backward these maps ARE the FPN backward's input, so in bf16
         # mode they are written in bf16 directly (no fp32 map + cast pass): the ROI part rounded once, the RPN head's few thousand
         # active pixels added on top in bf16 -- the two bf16 gradients the reference's autocast sums (aldi/trainer.py:79)
-        g_dt = T if (self.sparse_rpn_backward and T == torch.bfloat16) else torch.float32
+        g_dt = T if (self.knobs.sparse_rpn_backward and T == torch.bfloat16) else torch.float32
         gP_roi = [(torch.empty if c.R > 0 else torch.zeros)(f.shape, dtype=g_dt, device=dev) for f in c.P[:4]]
         if c.R > 0:
             g_extra = None
@@ -1287,7 +1310,7 @@ class RCNN:
             ops.roialign_backward(self.roi_feats(c, gP_roi), c.rois, c.R, POOL, g_pooled, c.N, rois_sorted=True, grad_dtype=g_dt)
         self._grads_final(["box_pred", "roi_heads.box_head.fc2", "roi_heads.box_head.fc1"])
         # ---- RPN head (shared weights over 5 levels)
-        if self.sparse_rpn_backward:
+        if self.knobs.sparse_rpn_backward:
             if sp_pre is not None:
                 main_ = torch.cuda.current_stream()
                 main_.wait_stream(aux)
@@ -1333,7 +1356,7 @@ class RCNN:
         gprev = {}
         for i, lvl in enumerate((2, 3, 4, 5)):
             self._wgrad(f"backbone.fpn_output{lvl}", c.prev[lvl], gP[i])
-        if self.level_groups:
+        if self.knobs.level_groups:
             gs = ops.conv2d_group([(gP[i], W.wt(f"backbone.fpn_output{lvl}"), dict(pad=1)) for i, lvl in enumerate((2, 3, 4, 5))])
             gprev.update(zip((2, 3, 4, 5), gs))
         else:
@@ -1341,7 +1364,7 @@ class RCNN:
                 gprev[lvl] = ops.conv2d(gP[i], W.wt(f"backbone.fpn_output{lvl}"), pad=1)
         sh = [tuple(gprev[lvl].shape) for lvl in (2, 3, 4, 5)]
         if (all(sh[i][1] == 2 * sh[i + 1][1] and sh[i][2] == 2 * sh[i + 1][2] for i in range(3)) and all(gprev[lvl].is_contiguous() for lvl in (2, 3, 4, 5))
-                and os.environ.get("ALDI_UPSAMPLE_CHAIN", "1") == "1"):
+                and self.knobs.upsample_chain):
             ops.upsample2_bwd_chain(gprev[2], gprev[3], gprev[4], gprev[5])      # one launch instead of three dependent ones (same bits)
         else:
             for lvl in (3, 4, 5):
@@ -1352,12 +1375,26 @@ class RCNN:
                           [f"backbone.fpn_lateral{l}" for l in (2, 3, 4, 5)])
         # ---- res5 .. res3 (stem + res2 frozen: FREEZE_AT=2)
         g = ops.conv2d(gprev[5], W.wt("backbone.fpn_lateral5"), **self._relu_mask(c, c.cs[3]))
-        blocks = c.blocks
-        bi = len(blocks) - 1
+
+        def close_stage(si, p, xin, g, g1):
+            gx = gx_pre.pop(si, None)
+            if gx is not None and gx.shape == xin.shape:
+                torch.cuda.current_stream().wait_event(gx_ev)
+                gx.record_stream(torch.cuda.current_stream())
+            else:
+                gx = None
+            return self._stage_input_grad(c, si, p, xin, g, g1, gprev[si + 1], gx)
+        self._stages_backward(c, g, close_stage, tail_split=self.knobs.wgrad_tail_split)
+
+    def _stages_backward(self, c: Ctx, g: torch.Tensor, close_stage, tail_split: int = 0):
+        """res5 .. res3 over the saved blocks, from g = d(loss)/d(C5) masked by C5's ReLU.  At a stage's first block its gradients are reported
+        final and g = close_stage(si, p, xin, g, g1) = d(loss)/d(the stage's input), masked (not for res3: the res2 output needs none)."""
+        W = self.wts
+        bi = len(c.blocks) - 1
         for si in (3, 2, 1):
             stage_names: List[str] = []
             for b in range(STAGE_BLOCKS[si] - 1, -1, -1):
-                p, xin, h1, h2, out, first = blocks[bi]
+                p, xin, h1, h2, out, first = c.blocks[bi]
                 bi -= 1
                 stage_names += [p + "conv3", p + "conv2", p + "conv1"] + ([p + "shortcut"] if first else [])
                 self._wgrad(p + "conv3", h2, g)
@@ -1365,7 +1402,7 @@ class RCNN:
                 self._wgrad(p + "conv2", h1, g2)
                 g1 = ops.conv2d(g2, W.wt(p + "conv2"), pad=1, **self._relu_mask(c, h1))
                 self._wgrad(p + "conv1", xin, g1)
-                if si == 1 and not first and self.wgrad_tail_split > 0 and (STAGE_BLOCKS[si] - b) % self.wgrad_tail_split == 0:
+                if si == 1 and not first and tail_split > 0 and (STAGE_BLOCKS[si] - b) % tail_split == 0:
                     # res3 is the LAST stage of the backward: launched as one group behind its last data gradient, its weight gradients
                     # (0.28 ms) run alone at the end of the step -- nothing is left to run beside them.  Launching the blocks done so
                     # far puts that part under the remaining blocks' data gradients (profiles/r05_timeline_spin.txt)
@@ -1375,19 +1412,13 @@ class RCNN:
                     self._grads_final(stage_names)
                     if si == 1:
                         break                                           # stage input (res2 output) needs no gradient
-                    gx = gx_pre.pop(si, None)
-                    if gx is not None and gx.shape == xin.shape:
-                        torch.cuda.current_stream().wait_event(gx_ev)
-                        gx.record_stream(torch.cuda.current_stream())
-                    else:
-                        gx = None
-                    g = self._stage_input_grad(c, si, p, xin, g, g1, gprev[si + 1], gx)
+                    g = close_stage(si, p, xin, g, g1)
                 else:
                     g = ops.conv2d(g1, W.wt(p + "conv1"), res=g, res_mode=1, **self._relu_mask(c, xin))
         self._join_wgrads()
 
     def _fold_stage_grad(self) -> bool:
-        return self.dtype == torch.bfloat16 and self.fused_stage_entrance
+        return self.dtype == torch.bfloat16 and self.knobs.fused_stage_entrance
 
     def _stage_input_grad(self, c: Ctx, si: int, p: str, xin: torch.Tensor, g: torch.Tensor, g1: torch.Tensor, gprev: torch.Tensor,
                           gx: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1398,57 +1429,37 @@ class RCNN:
         launch adds that as a zero-stuffed stride-2 residual (res_mode 3) -- no full-size zero map is cleared, scattered into twice and read back.
         Same bits: the pair rounds twice, as the two scattering launches do (out_scale > 1 takes the staged epilogue)."""
         W = self.wts
-        stride = W.layout.t[p + "conv1"].stride
-        lvl = si + 1
-        lat = W.wt(f"backbone.fpn_lateral{lvl}")
-        if self._fold_stage_grad() and stride == 2:
+        lat = W.wt(f"backbone.fpn_lateral{si + 1}")
+        if self._fold_stage_grad() and W.layout.t[p + "conv1"].stride == 2:
             gq = ops.conv2d(g1, W.wt(p + "conv1"), pre=(g, W.wt(p + "shortcut"), None, None, 1, 2))
             return ops.conv2d(gprev, lat, res=gq, res_mode=3, **self._relu_mask(c, xin))
+        gx = self._scatter_stage_grad(p, xin, g, g1, gx)
+        return ops.conv2d(gprev, lat, res=gx, res_mode=1, **self._relu_mask(c, xin))
+
+    def _scatter_stage_grad(self, p: str, xin: torch.Tensor, g: torch.Tensor, g1: torch.Tensor, gx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the shortcut's and conv1's data gradients of the stage entrance `p` (both 1x1 at the stage's stride), scattered into every stride-th
+        pixel of a zero map of xin's shape (gx: one cleared ahead of time); unmasked"""
+        W = self.wts
+        stride = W.layout.t[p + "conv1"].stride
         Hin, Win = xin.shape[1], xin.shape[2]
         if gx is None:
             gx = torch.zeros_like(xin)
         ops.conv2d(g, W.wt(p + "shortcut"), out=gx, out_scale=stride, out_hw=(Hin, Win))
         ops.conv2d(g1, W.wt(p + "conv1"), out=gx, out_scale=stride, out_hw=(Hin, Win), res=gx, res_mode=1)
-        return ops.conv2d(gprev, lat, res=gx, res_mode=1, **self._relu_mask(c, xin))
+        return gx
 
     def trunk_backward(self, c: Ctx, gC: Dict[int, Optional[torch.Tensor]]):
         """backward of the bare trunk (trunk_steps(..., fpn=False), fp32): gC[lvl] = d(loss)/d(C_lvl) for lvl in 3, 4, 5 (the stage outputs,
         post-ReLU; None = no gradient); weight gradients of res3..res5 accumulate as in `backward`, stem + res2 are frozen (FREEZE_AT = 2)"""
-        W = self.wts
         assert self.dtype == torch.float32, "the bare-trunk backward runs in the fp32 mode (the DETR path's AMP is off)"
+
         def masked(a, b, act):                     # (a + b) where act > 0; a, b nullable (not both)
             if a is None and b is None:
                 return None
             x, y = (a, b) if b is not None else (None, a)
             return ops.add_f32(x, y, torch.empty_like(act), relu_src=act)
-        blocks = c.blocks
-        bi = len(blocks) - 1
-        g = masked(gC.get(5), None, c.cs[3])
-        for si in (3, 2, 1):
-            stage_names: List[str] = []
-            for b in range(STAGE_BLOCKS[si] - 1, -1, -1):
-                p, xin, h1, h2, out, first = blocks[bi]
-                bi -= 1
-                stage_names += [p + "conv3", p + "conv2", p + "conv1"] + ([p + "shortcut"] if first else [])
-                self._wgrad(p + "conv3", h2, g)
-                g2 = ops.conv2d(g, W.wt(p + "conv3"), mask=h2)
-                self._wgrad(p + "conv2", h1, g2)
-                g1 = ops.conv2d(g2, W.wt(p + "conv2"), pad=1, mask=h1)
-                self._wgrad(p + "conv1", xin, g1)
-                if first:
-                    self._wgrad(p + "shortcut", xin, g)
-                    self._grads_final(stage_names)
-                    if si == 1:
-                        break                                           # stage input (res2 output) needs no gradient
-                    stride = W.layout.t[p + "conv1"].stride
-                    Hin, Win = xin.shape[1], xin.shape[2]
-                    gx = torch.zeros_like(xin)
-                    ops.conv2d(g, W.wt(p + "shortcut"), out=gx, out_scale=stride, out_hw=(Hin, Win))
-                    ops.conv2d(g1, W.wt(p + "conv1"), out=gx, out_scale=stride, out_hw=(Hin, Win), res=gx, res_mode=1)
-                    g = masked(gC.get(si + 1), gx, xin)                # this stage's input is C_{si+1}: its own gradient joins here
-                else:
-                    g = ops.conv2d(g1, W.wt(p + "conv1"), res=g, res_mode=1, mask=xin)
-        self._join_wgrads()
+        close = lambda si, p, xin, g, g1: masked(gC.get(si + 1), self._scatter_stage_grad(p, xin, g, g1), xin)   # C_{si+1}'s own gradient joins here
+        self._stages_backward(c, masked(gC.get(5), None, c.cs[3]), close)
 
     @staticmethod
     def _relu_mask(c: Ctx, act: torch.Tensor) -> dict:
@@ -1495,15 +1506,17 @@ class RCNN:
         return self._rpn_sparse_finish(c, gP_roi, self._rpn_sparse_prepare(c))
 
     def _aux_stream(self):
+        # lazy on the PRESENCE of the instance attribute `_aux_side` (None = no side stream): single-stream profiling runs set it to None
+        # and delete it afterwards to have it created again, so it is neither declared in `_init_common` nor a property
         if not hasattr(self, "_aux_side"):
-            self._aux_side = torch.cuda.Stream(device=self.device) if os.environ.get("ALDI_AUX_STREAM", "1") == "1" and torch.device(self.device).type == "cuda" else None
+            self._aux_side = torch.cuda.Stream(device=self.device) if self.knobs.aux_stream and torch.device(self.device).type == "cuda" else None
         return self._aux_side
 
     def _grads_final(self, names: List[str]):
         """tell the gradient exchange (if one is attached: data-parallel fused step) that these layers' gradients are
         complete for this step -- every kernel writing them has been enqueued."""
         self._flush_wgrads()
-        cb = getattr(self, "grad_ready", None)
+        cb = self.grad_ready
         if cb is None:
             return
         # Producer events instead of a join: the gradient exchange waits for the weight-gradient stream and for this point of
@@ -1524,6 +1537,23 @@ class RCNN:
             self._join_wgrads()
             cb(self.wts.layout.ranges(names))
 
+    @contextlib.contextmanager
+    def _on_wgrad_stream(self, temps=()):
+        """run the body on the weight-gradient stream, behind everything the current stream holds so far (no such stream: in place).
+        temps = what the body reads of the current stream's allocator (gradients, gathered rows; not saved activations)"""
+        side = self._wgrad_stream()
+        if side is None:
+            yield
+            return
+        ev = torch.cuda.Event()
+        ev.record()                                  # the body's inputs are complete once the current stream gets here
+        side.wait_event(ev)
+        for t in temps:
+            t.record_stream(side)
+        with torch.cuda.stream(side):
+            yield
+        self._wgrad_pending = True
+
     def _wgrad(self, name: str, x: torch.Tensor, g: torch.Tensor, flat: bool = False, temp_x: bool = False):
         """weight (+ bias) gradient of one layer (`flat`: x holds im2col rows [S][KH*KW*Cin], the gradient is a plain GEMM).
         Nothing reads these results before the optimizer, so (a) in bf16 mode they are only QUEUED here and launched per layer
@@ -1533,82 +1563,48 @@ class RCNN:
         p = W.layout.t[name]
         geo = dict(KH=1, KW=1, stride=1, pad=0) if flat else dict(KH=p.kk, KW=p.kk, stride=p.stride, pad=p.pad)
         geo["scale"] = W.scale(name)
-        if (not flat and p.kk == 1 and p.stride == 2 and p.pad == 0 and self.dtype == torch.bfloat16 and getattr(self, "group_wgrad", False)
-                and os.environ.get("ALDI_WGRAD_SUBSAMPLE", "1") == "1"):
+        grouped = self.knobs.group_wgrad and self.dtype == torch.bfloat16
+        if not flat and p.kk == 1 and p.stride == 2 and p.pad == 0 and grouped and self.knobs.wgrad_subsample:
             # a stride-2 1x1 conv (first block of res3..res5: conv1 and the shortcut read the same input) sees every other pixel:
             # gather those ONCE into a dense map and its weight gradient is a plain GEMM that joins the stage's grouped launch,
             # instead of two launches of the generic gather kernel per stage (6 x ~60 us)
-            cache = self.__dict__.setdefault("_sub_cache", {})
-            hit = cache.get(id(x))
+            hit = self._sub_cache.get(id(x))
             if hit is None or hit[0] is not x:
-                side_ = self._wgrad_stream()
-                if side_ is not None and os.environ.get("ALDI_WGRAD_SUBSAMPLE_SIDE", "1") == "1":
-                    # only the weight gradients read the gathered map: on THEIR stream, not as one more dependent launch of the
-                    # data-gradient chain (x is a saved activation: complete long before this point of the main stream)
-                    ev_ = torch.cuda.Event()
-                    ev_.record()
-                    side_.wait_event(ev_)
-                    with torch.cuda.stream(side_):
-                        hit = (x, ops.subsample2(x))
-                else:
+                # only the weight gradients read the gathered map: on THEIR stream, not as one more dependent launch of the
+                # data-gradient chain (x is a saved activation: complete long before this point of the main stream)
+                with self._on_wgrad_stream() if self.knobs.wgrad_subsample_side else contextlib.nullcontext():
                     hit = (x, ops.subsample2(x))
-                cache.clear()
-                cache[id(x)] = hit
+                self._sub_cache.clear()
+                self._sub_cache[id(x)] = hit
             x, temp_x = hit[1], True
             geo.update(stride=1)
-        if getattr(self, "group_wgrad", False) and self.dtype == torch.bfloat16:
-            fused_bias = p.bias and os.environ.get("ALDI_WGRAD_BIAS_FUSED", "1") == "1"    # (0: the separate column-sum launches, for A/B runs)
+        if grouped:
+            fused_bias = p.bias and self.knobs.wgrad_bias_fused    # (0: the separate column-sum launches, for A/B runs)
             if fused_bias:
                 geo["db"] = W.gb(name)
             self._wg_queue.append((x, g, W.gw(name), geo, W.gb(name) if p.bias and not fused_bias else None, temp_x))
             return
-        side = self._wgrad_stream()
         if p.bias:
             geo["db"] = W.gb(name)                   # the bias gradient rides in the same launch (ones column; csrc/wgrad.hip)
-        if side is None:
+        with self._on_wgrad_stream([g, x] if temp_x else [g]):
             ops.conv_wgrad(x, g, W.gw(name), **geo)
-            return
-        ev = torch.cuda.Event()
-        ev.record()                                  # g (and x) are complete once the main stream gets here
-        side.wait_event(ev)
-        g.record_stream(side)                        # g is a temporary of the main stream's allocator
-        if temp_x:
-            x.record_stream(side)                    # x is a temporary too (gathered rows), not a saved activation
-        with torch.cuda.stream(side):
-            ops.conv_wgrad(x, g, W.gw(name), **geo)
-        self._wgrad_pending = True
 
     def _flush_wgrads(self):
         """launch the queued weight gradients: one grouped launch (+ the bias sums) on the weight-gradient stream"""
-        q = getattr(self, "_wg_queue", None)
+        q = self._wg_queue
         if not q:
             return
         self._wg_queue = []
-        side = self._wgrad_stream()
-
-        def launch():
+        with self._on_wgrad_stream([t for x, g, _, _, _, temp_x in q for t in ((g, x) if temp_x else (g,))]):
             ops.conv_wgrad_group([(x, g, dw, geo) for x, g, dw, geo, _, _ in q])
             for _, g, _, _, gb, _ in q:
                 if gb is not None:
                     ops.bias_grad(g, gb)
-        if side is None:
-            launch()
-            return
-        ev = torch.cuda.Event()
-        ev.record()
-        side.wait_event(ev)
-        for x, g, _, _, _, temp_x in q:
-            g.record_stream(side)
-            if temp_x:
-                x.record_stream(side)
-        with torch.cuda.stream(side):
-            launch()
-        self._wgrad_pending = True
 
     def _wgrad_stream(self):
+        # lazy on the PRESENCE of the instance attribute `_wg_side`, as `_aux_stream`; `_wgrad_pending` stays plain and assignable for such runs
         if not hasattr(self, "_wg_side"):
-            self._wg_side = (torch.cuda.Stream(device=self.device, priority=int(os.environ.get("ALDI_WGRAD_PRIO", "0")))
-                             if os.environ.get("ALDI_WGRAD_STREAM", "1") == "1" else None)
+            self._wg_side = torch.cuda.Stream(device=self.device, priority=self.knobs.wgrad_prio) if self.knobs.wgrad_stream else None
             self._wgrad_pending = False
         return self._wg_side
 

@@ -21,6 +21,7 @@ from .vit import SimpleFeaturePyramid, ViT, VitConfig, VitParams
 class FlatParamRCNN(RCNN):
     """engine.RCNN over a `VitParams` flat container (detectron2-named parameters, packed predictor rows) instead of the R50
     `Weights` / `ParamLayout`: shared by the ViTDet and ConvNeXt-FPN detectors, which override the architecture-specific methods"""
+    sparse_rpn_backward = False             # (their RPN head's backward is their own, dense one)
 
     def _init_flat(self, params: VitParams, num_classes: int, seed: int):
         cfg = params.cfg
@@ -28,12 +29,10 @@ class FlatParamRCNN(RCNN):
         self.vp = params
         self.wts = params                       # what engine.RCNN calls `weights` (only touched by the overrides)
         self.K = num_classes
-        self.device, self.dtype = params.device, torch.bfloat16
+        self.dtype = torch.bfloat16
         self.Cp = (5 * num_classes + 1 + 15) // 16 * 16
         self.Ch = (5 * cfg.num_anchors + 15) // 16 * 16
-        self._anchor_cache, self._ws = {}, {}
-        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
-        torch.set_num_threads(1)
+        self._init_common(params.device)
         self.has_img_da = self.has_ins_da = False
         self.drop_gen = torch.Generator().manual_seed(seed)     # stochastic-depth masks (host-drawn, see ViT.drop_path_scales)
 
@@ -230,7 +229,7 @@ class VitDetRCNN(FlatParamRCNN):
         ops.subsample2_bwd(gP[4], gP[3])                               # p6 = p5[:, ::2, ::2]
         for l in range(4):
             ops.add_f32(gP[l], gP_roi[l], gP[l])
-        cb = getattr(self, "grad_ready", None)
+        cb = self.grad_ready
         if cb is not None:                                             # heads are final: start their exchange under the trunk backward
             cb(self.vp.ranges([n for n in self.vp.spec if n.startswith(("proposal_generator.", "roi_heads."))]))
         gx = self.sfp.backward(c.sfp_ctx, gP[:4])

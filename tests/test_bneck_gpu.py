@@ -67,8 +67,8 @@ def test_trunk_with_fused_res2_matches_layerwise():
     st, sizes, _ = m.stage_images([d["image"] for d in data])
     outs = {}
     for fused in (True, False):
-        m.fused_res2 = fused
-        c = m.trunk(st, sizes, save=False)
+        with m.with_knobs(fused_res2=fused):
+            c = m.trunk(st, sizes, save=False)
         torch.cuda.synchronize()
         outs[fused] = [p.float() for p in c.P]
     for a, b in zip(outs[True], outs[False]):

@@ -683,9 +683,9 @@ def test_sparse_rpn_head_backward_equals_dense(dtype, tol):
     scales = {"loss_cls": 1.0, "loss_box_reg": 1.0, "loss_rpn_cls": 1.0, "loss_rpn_loc": 1.0}
     grads = {}
     for sparse in (True, False):
-        m.sparse_rpn_backward = sparse
         wts.zero_grad()
-        m.backward(c, scales)
+        with m.with_knobs(sparse_rpn_backward=sparse):
+            m.backward(c, scales)
         torch.cuda.synchronize()
         grads[sparse] = wts.grad.clone()
     assert int(m.err) == 0
@@ -699,9 +699,9 @@ def test_sparse_rpn_head_backward_equals_dense(dtype, tol):
             assert float((a[lo:hi] - ref).abs().max()) <= tol * float(ref.abs().max()), (n, float((a[lo:hi] - ref).abs().max()), float(ref.abs().max()))
     # RPN-only losses: with the ROI heads' losses off the ONLY gradient source is the sparse path
     for sparse in (True, False):
-        m.sparse_rpn_backward = sparse
         wts.zero_grad()
-        m.backward(c, {"loss_rpn_cls": 1.0, "loss_rpn_loc": 0.5})
+        with m.with_knobs(sparse_rpn_backward=sparse):
+            m.backward(c, {"loss_rpn_cls": 1.0, "loss_rpn_loc": 0.5})
         torch.cuda.synchronize()
         grads[sparse] = wts.grad.clone()
     a, b = grads[True], grads[False]

@@ -97,13 +97,13 @@ def test_trunk_with_shortcut_fold_equals_trunk_without():
     w = Weights(lay, torch.device(DEV), torch.bfloat16, trainable=True)
     w.load_state_dict(syn.init_state_dict(K, seed=1))
     m = RCNN(w, K)
-    assert m.fused_res2 and m.fused_res2_shortcut
+    assert m.knobs.fused_res2 and m.knobs.fused_res2_shortcut
     _, data, _, _ = syn.make_batch(2, 0, H, W, K, seed=0)
     st, sizes, _ = m.stage_images([d["image"] for d in data])
     outs = {}
     for fold in (True, False):
-        m.fused_res2_shortcut = fold
-        c = m.trunk(st, sizes, save=False)
+        with m.with_knobs(fused_res2_shortcut=fold):
+            c = m.trunk(st, sizes, save=False)
         torch.cuda.synchronize()
         outs[fold] = c.P
     assert len(outs[True]) == 5 and float(outs[False][0].float().abs().max()) > 0

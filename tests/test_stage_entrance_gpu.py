@@ -119,7 +119,7 @@ def model():
     w = Weights(ParamLayout(K), torch.device(DEV), torch.bfloat16, trainable=True)
     w.load_state_dict(syn.init_state_dict(K, seed=1))
     m = RCNN(w, K)
-    assert m.fused_stage_entrance
+    assert m.knobs.fused_stage_entrance
     _, data, _, _ = syn.make_batch(2, 0, H, W, K, seed=0)
     st, sizes, _ = m.stage_images([d["image"] for d in data])
     return m, st, sizes
@@ -132,22 +132,19 @@ def test_trunk_with_stage_entrance_fold_equals_trunk_without(model, save):
     from aldi_amd import _lib as L
     m, st, sizes = model
     outs, bits, names = {}, {}, {}
-    try:
-        for fold in (True, False):
-            m.fused_stage_entrance = fold
-            seen = []
-            conv = m.conv
-            m.conv = lambda x, name, **kw: (conv(x, name, **kw), seen.append((name, L.last_dispatch())))[0]
-            try:
+    for fold in (True, False):
+        seen = []
+        conv = m.conv
+        m.conv = lambda x, name, **kw: (conv(x, name, **kw), seen.append((name, L.last_dispatch())))[0]
+        try:
+            with m.with_knobs(fused_stage_entrance=fold):
                 c = m.trunk(st, sizes, save=save)
-            finally:
-                del m.conv
-            torch.cuda.synchronize()
-            outs[fold], names[fold] = c.P, seen
-            if save:
-                bits[fold] = [c.out_bits[blk[4].data_ptr()] for blk in c.blocks]
-    finally:
-        m.fused_stage_entrance = True
+        finally:
+            del m.conv
+        torch.cuda.synchronize()
+        outs[fold], names[fold] = c.P, seen
+        if save:
+            bits[fold] = [c.out_bits[blk[4].data_ptr()] for blk in c.blocks]
     assert sum(n.endswith("shortcut") for n, _ in names[False]) == 3 and not any(n.endswith("shortcut") for n, _ in names[True])
     assert sum(d.startswith("igemm_pair<") for _, d in names[True]) == 3 and not any(d.startswith("igemm_pair<") for _, d in names[False])
     assert len(outs[True]) == 5 and float(outs[False][0].float().abs().max()) > 0
@@ -173,14 +170,11 @@ def test_stage_input_gradient_folded_equals_three_scattering_launches(model, si)
     rnd = lambda like, ch=None: torch.randn(*like.shape[:3], ch or like.shape[3], generator=gen).to(torch.bfloat16).to(DEV)
     g, g1, gprev = rnd(out), rnd(h1), rnd(xin, FPN_C)
     res = {}
-    try:
-        for fold in (True, False):
-            m.fused_stage_entrance = fold
+    for fold in (True, False):
+        with m.with_knobs(fused_stage_entrance=fold):
             res[fold] = m._stage_input_grad(c, si, p, xin, g, g1, gprev)
             res[fold, "name"] = L.last_dispatch()
             torch.cuda.synchronize()
-    finally:
-        m.fused_stage_entrance = True
     assert res[True, "name"] == res[False, "name"]        # the lateral's data gradient keeps its kernel
     assert res[True].shape == xin.shape and 0.05 < float((res[False] != 0).float().mean()) < 0.95
     assert torch.equal(res[True], res[False])
