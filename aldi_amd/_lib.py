@@ -191,6 +191,12 @@ class ClipChunk(C.Structure):
 NORM_L2, NORM_INF = 0, 1
 
 
+class BoxTfm(C.Structure):
+    """aldi_box_tfm (include/aldi_hip.h): one (image, view)'s inverse box transform"""
+    _fields_ = [("flip_w", c_float), ("sx0", c_float), ("sy0", c_float), ("sx1", c_float), ("sy1", c_float),
+                ("clip_w", c_float), ("clip_h", c_float), ("pad", c_int)]
+
+
 class BottleneckArgs(C.Structure):
     _fields_ = [("x", c_void_p), ("res", c_void_p), ("y", c_void_p), ("w1", c_void_p), ("w2", c_void_p), ("w3", c_void_p),
                 ("b1", c_void_p), ("b2", c_void_p), ("b3", c_void_p),

@@ -195,6 +195,8 @@ def add_aldi_config(cfg: CfgNode):
     # detections above DOMAIN_ADAPT.TEACHER.THRESHOLD (Prec50, Rec50: the pseudo labels the student sees), from either evaluator
     # (aldi_amd/evaluation.py summarize_bbox); off: the six AP numbers only
     _C.TEST.EVAL_DETAIL = False
+    if "AUG" not in _C.TEST:                                      # detectron2 defaults; read by aldi_amd/tta.py (`test()` does not read ENABLED)
+        _C.TEST.AUG = CN({"ENABLED": False, "MIN_SIZES": (400, 500, 600, 700, 800, 900, 1000, 1100, 1200), "MAX_SIZE": 4000, "FLIP": True})
 
     _C.EMA = CN()
     _C.EMA.ENABLED = False

@@ -415,7 +415,6 @@ class DeformableDETR:
     def inference(self, batched_inputs: List[Dict], do_postprocess: bool = False, pl_thresh: float = 2.0):
         """-> list[Instances] (top-100 detections of the last decoder layer, absolute xyxy in network-input pixels); the detections scoring
         above pl_thresh are also left on the device as this inference's pseudo labels (`_last_inference.pseudo`)"""
-        assert not do_postprocess, "aldi_amd keeps detections in network-input space (the hot path calls do_postprocess=False)"
         with torch.no_grad():
             images = [b["image"] for b in batched_inputs]
             ctr, sizes, mask = self._trunk(images, save=False)
@@ -441,6 +440,11 @@ class DeformableDETR:
             c = Ctx()
             c.sizes, c.pseudo = sizes, {"boxes": pb, "classes": pc, "scores": ps, "count": cnt}
             self._last_inference = c
+            if do_postprocess:                                     # detectron2's [{"instances": ...}] in each input's "height" / "width" pixels
+                from ..postprocess import output_sizes, postprocess_batch
+                full = torch.full((B,), k, dtype=torch.int32, device=self.device)
+                return [{"instances": r} for r in postprocess_batch(xyxy, scores, labels.to(torch.int32), full, list(sizes),
+                                                                    output_sizes(batched_inputs, sizes))]
             out = []
             for i in range(B):
                 inst = Instances(sizes[i])

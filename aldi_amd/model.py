@@ -269,13 +269,18 @@ class GeneralizedRCNN:
         return wire_losses(h, self.engine.loss_dict(c))
 
     def inference(self, batched_inputs: List[Dict], do_postprocess: bool = False, pl_thresh: float = 2.0):
-        """-> list[Instances] with pred_boxes / scores / pred_classes (network-input pixel space)."""
-        assert not do_postprocess, "aldi_amd keeps detections in network-input space (the hot path calls do_postprocess=False)"
+        """-> list[Instances] with pred_boxes / scores / pred_classes (network-input pixel space); with `do_postprocess`,
+        detectron2's [{"instances": Instances}, ...] in the pixels of each input's "height" / "width" (postprocess.py)."""
         with torch.no_grad():
             images, _ = self._split_inputs(batched_inputs)
             self.roi_heads.fire_pre()                       # ManualSeed fires on every roi_heads forward (aldi/helpers.py:25-26)
             c = self.engine.inference(images, pl_thresh)
             self._last_inference = c
+            if do_postprocess:
+                from .postprocess import output_sizes, postprocess_batch
+                d = c.det
+                return [{"instances": r} for r in postprocess_batch(d.boxes, d.scores, d.classes, d.count, list(c.sizes),
+                                                                    output_sizes(batched_inputs, c.sizes))]
             out = []
             cnt = c.det.count.tolist()
             for i, n in enumerate(cnt):

@@ -668,6 +668,25 @@ def detections(pred, Cp, K, props, pcount, P, N, img_hw, weights4, score_thresh,
            pl_boxes.shape[1], _p(err), stream_ptr())
 
 
+# ------------------------------------------------------------------------------- inference API (csrc/infer.hip)
+def detector_postprocess(boxes, scores, classes, count, tfm, out_boxes, out_scores, out_classes, out_count):
+    """boxes [N][D][4] f32, scores [N][D] f32, classes [N][D] i32, count [N] i32, tfm: device bytes of N aldi_box_tfm"""
+    N, D = int(boxes.shape[0]), int(boxes.shape[1])
+    L.call("aldi_detector_postprocess", _p(boxes), _p(scores), _p(classes), _p(count), N, D, _p(tfm),
+           _p(out_boxes), _p(out_scores), _p(out_classes), _p(out_count), stream_ptr())
+
+
+def tta_merge_workspace(B, A, D) -> int:
+    return int(L.lib.aldi_tta_merge_workspace(B, A, D))
+
+
+def tta_merge(boxes, scores, classes, count, tfm, K, score_floor, nms_thresh, topk, workspace, out_boxes, out_scores, out_classes, out_count):
+    """boxes [B][A][D][4] f32, scores / classes [B][A][D], count [B][A] i32, tfm: device bytes of B * A aldi_box_tfm"""
+    B, A, D = int(boxes.shape[0]), int(boxes.shape[1]), int(boxes.shape[2])
+    L.call("aldi_tta_merge", _p(boxes), _p(scores), _p(classes), _p(count), _p(tfm), B, A, D, int(K), float(score_floor), float(nms_thresh),
+           int(topk), _p(workspace), _p(out_boxes), _p(out_scores), _p(out_classes), _p(out_count), stream_ptr())
+
+
 # ------------------------------------------------------------------------------- ALDI losses
 def rpn_distill_loss(geom, s_head, t_head, grad, labels, N, obj_T, n_valid, n_fg, do_obj, do_reg, grad_scale, loss2, counts_dev=None):
     """counts_dev: device int32[2] {n_valid, n_fg} overriding the two host ints (graph-captured steps)"""

@@ -945,6 +945,20 @@ class ALDITrainer(DefaultTrainer):
             results[name] = inference_on_dataset(model, loader[rank::world] if world > 1 else loader, ev)
         return results[names[0]] if len(results) == 1 else results
 
+    @classmethod
+    def test_with_TTA(cls, cfg, model):
+        """detectron2 tools/train_net.py `Trainer.test_with_TTA`: the model wrapped in GeneralizedRCNNWithTTA (aldi_amd/tta.py), evaluators
+        writing to <OUTPUT_DIR>/inference_TTA, result keys suffixed "_TTA".  The wrapper's Instances are in the original image's
+        coordinates with image_size = (height, width), so the evaluators' rescaling is by exactly 1."""
+        from .tta import GeneralizedRCNNWithTTA
+        logging.getLogger(__name__).info("Running inference with test-time augmentation ...")
+        wrapped = GeneralizedRCNNWithTTA(cfg, model)
+        names = list(cfg.DATASETS.TEST) or ["synthetic_val"]
+        folder = os.path.join(cfg.OUTPUT_DIR, "inference_TTA")
+        evaluators = [cls.build_evaluator(cfg, name, output_folder=folder, dataset_dicts=cls.build_test_loader(cfg, name)[1]) for name in names]
+        res = cls.test(cfg, wrapped, evaluators)
+        return OrderedDict({k + "_TTA": v for k, v in res.items()})
+
     def after_step(self):
         """aldi/trainer.py:173-196: EvalHook on the EMA model (the student without EMA) every TEST.EVAL_PERIOD iterations and
         after the last one; BestCheckpointer on `bbox/AP50` (one test set) or `<test_set>/bbox/AP50` (several), "max",

@@ -659,6 +659,37 @@ int aldi_geom_plan(const int* ybounds, int h, int new_h, int* fused);
 int aldi_geom_batch_resize(const aldi_geom_desc* desc, int n, const int* tables, int ntiles, int nh_blocks, int nv_blocks, aldi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Inference API (aldi_amd/postprocess.py, predictor.py, tta.py; csrc/infer.hip): detections brought back to the original
+ * image, and the class-wise merge of the detections of several test-time views.  PARITY UNPINNED restatements of detectron2
+ * v0.6 (detector_postprocess; TransformList.inverse().apply_box on a float32 array; GeneralizedRCNNWithTTA._merge_detections),
+ * all in float32, one operation per stage.  One descriptor per (image, view), uploaded by the caller; the host forms every
+ * scale as a double ratio and rounds it once to float32 (postprocess.box_tfm).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct { float flip_w;        /* < 0: no flip; else x -> flip_w - x first                         */
+                 float sx0, sy0;      /* then x *= sx0, y *= sy0                                           */
+                 float sx1, sy1;      /* then x *= sx1, y *= sy1  (1.0f = exact no-op)                     */
+                 float clip_w, clip_h;/* then clamp x to [0, clip_w], y to [0, clip_h]                     */
+                 int   pad; } aldi_box_tfm;
+/* Per image n, rows j < min(count[n], D) of boxes [N][D][4] (XYXY) / scores [N][D] / classes [N][D]: the box through tfm[n]
+ * (flip, the two scales, re-ordered to (min x, min y, max x, max y), clamped), kept when (x2 - x1) > 0 && (y2 - y1) > 0,
+ * compacted in order into out_* (same shapes; they must not overlap the inputs).  Rows from out_count[n] on: zero box, zero
+ * score, class -1.  All pointers device memory; N == 0 is a no-op. */
+int aldi_detector_postprocess(const float* boxes, const float* scores, const int* classes, const int* count, int N, int D,
+                              const aldi_box_tfm* tfm, float* out_boxes, float* out_scores, int* out_classes, int* out_count,
+                              aldi_stream_t stream);
+/* bytes of aldi_tta_merge's workspace; 0 when the shape is one aldi_tta_merge refuses */
+size_t aldi_tta_merge_workspace(int B, int A, int D);
+/* fast_rcnn_inference_single_image over the union of A views' detections, for each of B original images.  boxes [B][A][D][4],
+ * scores / classes [B][A][D], count [B][A], tfm [B][A].  A row (flat index a * D + j, j < min(count, D)) is a candidate when
+ * its box and score are finite, 0 <= class < K and, after its box went through its view's tfm, score > score_floor (strict).
+ * Candidates are ordered by (score descending, flat index ascending); class-aware NMS suppresses at IoU > nms_thresh (strict);
+ * the first topk survivors go to out_boxes [B][topk][4] / out_scores / out_classes [B][topk] in that order, the rows from
+ * out_count[b] on are zero boxes, zero scores, class -1.  A * D above 8192 is ALDI_ERR_ARG. */
+int aldi_tta_merge(const float* boxes, const float* scores, const int* classes, const int* count, const aldi_box_tfm* tfm,
+                   int B, int A, int D, int K, float score_floor, float nms_thresh, int topk, void* workspace,
+                   float* out_boxes, float* out_scores, int* out_classes, int* out_count, aldi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * COCO box-AP evaluation (aldi_amd/evaluation.py DeviceCOCOEvaluator, `TEST.DEVICE_EVAL`): pycocotools' COCOeval for
  * iouType="bbox" as the host evaluator states it (evaluate_img, accumulate), in fp64 with the host's operations in the
  * host's order, so precision / recall are equal to the host's.  Area ranges, IoU and recall thresholds are passed in as
