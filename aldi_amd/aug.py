@@ -532,14 +532,13 @@ class ResizeShortestEdge:
 
 
 class RandomFlip:
-    """detectron2 RandomFlip (parity unpinned): one uniform(0, 1) draw against `prob`; the device path flips horizontally only."""
+    """detectron2 RandomFlip (parity unpinned): one uniform(0, 1) draw against `prob`.  A vertical flip is a stage of the full
+    chain (`get_view_augs` / `draw_view_params`) only: the device weak view flips horizontally."""
     def __init__(self, prob=0.5, *, horizontal=True, vertical=False):
         if horizontal and vertical:
             raise ValueError("RandomFlip: cannot do both horizontal and vertical")
         if not horizontal and not vertical:
             raise ValueError("RandomFlip: at least one of horizontal or vertical has to be True")
-        if vertical:
-            raise ValueError("RandomFlip: the device weak view (AUG.DEVICE_WEAK) flips horizontally only")
         self.prob, self.horizontal, self.vertical = prob, horizontal, vertical
 
     def get_params(self, np_rng=np.random) -> bool:
@@ -589,10 +588,11 @@ def draw_weak_params(augs, h: int, w: int, np_rng=np.random) -> WeakParams:
     for a in augs:
         if isinstance(a, ResizeShortestEdge):
             new_h, new_w = a.get_params(new_h, new_w, np_rng)
-        elif isinstance(a, RandomFlip):
+        elif isinstance(a, RandomFlip) and not a.vertical:
             flip ^= a.get_params(np_rng)
         else:
-            raise ValueError(f"draw_weak_params: {type(a).__name__} is not a stage of get_weak_augs")
+            raise ValueError(f"draw_weak_params: {'a vertical RandomFlip' if isinstance(a, RandomFlip) else type(a).__name__} "
+                             "is not a stage of get_weak_augs (the full chain is drawn by draw_view_params)")
     return WeakParams(h, w, new_h, new_w, flip)
 
 
@@ -745,10 +745,12 @@ def transform_boxes(boxes: np.ndarray, p: WeakParams) -> np.ndarray:
     return np.minimum(out, [p.new_w, p.new_h, p.new_w, p.new_h])
 
 
-def transform_instances(inst: dict, p: WeakParams) -> dict:
-    """the record's instances under the weak view: boxes through `transform_boxes`, cast to float32, those with width or
-    height <= 1e-5 dropped with their classes (detectron2 filter_empty_instances), image_size = the new size"""
-    boxes = torch.from_numpy(transform_boxes(inst["gt_boxes"].detach().cpu().numpy(), p)).to(torch.float32)
+def transform_instances(inst: dict, p) -> dict:
+    """the record's instances under the weak view: boxes through `transform_boxes` (a ViewParams: `transform_view_boxes`), cast to
+    float32, those with width or height <= 1e-5 -- a box the window cut away, say -- dropped with their classes (detectron2
+    filter_empty_instances), image_size = the new size"""
+    tfm = transform_boxes if isinstance(p, WeakParams) else transform_view_boxes
+    boxes = torch.from_numpy(tfm(inst["gt_boxes"].detach().cpu().numpy(), p)).to(torch.float32)
     keep = ((boxes[:, 2] - boxes[:, 0]) > 1e-5) & ((boxes[:, 3] - boxes[:, 1]) > 1e-5)
     out = dict(inst)
     out["image_size"] = (p.new_h, p.new_w)
@@ -757,3 +759,139 @@ def transform_instances(inst: dict, p: WeakParams) -> dict:
         if key not in ("gt_boxes", "image_size") and torch.is_tensor(val) and val.dim() >= 1 and val.shape[0] == boxes.shape[0]:
             out[key] = val[keep]
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the full chain, host half
+# detectron2's whole train-time mapper chain for a decoded image -- [RandomCrop] + ResizeShortestEdge + [RandomFlip horizontal |
+# vertical] -- as DRAWS and box arithmetic only: what a view with a source window has to be told, and what it does to the boxes.
+# Nothing here touches the device; `launch_weak_views` runs the two-stage chain only.  The two-stage entries above stay as they are.
+# The detectron2 pieces restate the published v0.6 behaviour: PARITY UNPINNED.
+class RandomCrop:
+    """detectron2 RandomCrop (parity unpinned).  `get_params` draws from `np_rng` what `get_transform` draws from np.random, in
+    its order: the crop size (relative_range: rand(2); absolute_range: randint for the height, then for the width), then
+    randint(h - ch + 1) for y0, then randint(w - cw + 1) for x0."""
+    TYPES = ("relative_range", "relative", "absolute", "absolute_range")
+
+    def __init__(self, crop_type: str, crop_size):
+        if crop_type not in self.TYPES:
+            raise ValueError(f"RandomCrop: crop_type {crop_type!r} is none of {self.TYPES}")
+        crop_size = tuple(crop_size)
+        if len(crop_size) != 2:
+            raise ValueError(f"RandomCrop: crop_size must be two values, got {crop_size}")
+        if crop_type == "absolute_range" and not crop_size[0] <= crop_size[1]:
+            raise ValueError(f"RandomCrop: absolute_range needs crop_size[0] <= crop_size[1], got {crop_size}")
+        self.crop_type, self.crop_size = crop_type, crop_size
+
+    def get_crop_size(self, h: int, w: int, np_rng=np.random) -> Tuple[int, int]:
+        if self.crop_type == "relative":
+            ch, cw = self.crop_size
+            return int(h * ch + 0.5), int(w * cw + 0.5)
+        if self.crop_type == "relative_range":
+            crop_size = np.asarray(self.crop_size, dtype=np.float32)
+            ch, cw = crop_size + np_rng.rand(2) * (1 - crop_size)
+            return int(h * ch + 0.5), int(w * cw + 0.5)
+        if self.crop_type == "absolute":
+            return min(int(self.crop_size[0]), h), min(int(self.crop_size[1]), w)
+        ch = int(np_rng.randint(min(h, self.crop_size[0]), min(h, self.crop_size[1]) + 1))
+        cw = int(np_rng.randint(min(w, self.crop_size[0]), min(w, self.crop_size[1]) + 1))
+        return ch, cw
+
+    def get_params(self, h: int, w: int, np_rng=np.random) -> Tuple[int, int, int, int]:
+        """-> (y0, x0, ch, cw)"""
+        ch, cw = self.get_crop_size(h, w, np_rng)
+        if not (1 <= ch <= h and 1 <= cw <= w):                          # (detectron2 asserts h >= croph and w >= cropw)
+            raise ValueError(f"RandomCrop: crop {ch}x{cw} ({self.crop_type} {self.crop_size}) does not fit the {h}x{w} image")
+        y0 = int(np_rng.randint(h - ch + 1))
+        x0 = int(np_rng.randint(w - cw + 1))
+        return y0, x0, ch, cw
+
+
+def get_view_augs(cfg, is_train: bool) -> list:
+    """detectron2's `DatasetMapper.from_config` chain: [RandomCrop] when training and INPUT.CROP.ENABLED, then
+    `utils.build_augmentation`: ResizeShortestEdge, and RandomFlip (horizontal or vertical) when training unless INPUT.RANDOM_FLIP
+    is "none".  Everything `get_weak_augs` refuses is a stage here."""
+    inp = cfg.INPUT
+    flip = inp.get("RANDOM_FLIP", "horizontal")
+    if flip not in ("horizontal", "vertical", "none"):
+        raise ValueError(f"unknown INPUT.RANDOM_FLIP {flip!r}")
+    augs = []
+    crop = inp.get("CROP", {})
+    if is_train and crop.get("ENABLED", False):
+        augs.append(RandomCrop(crop.TYPE, crop.SIZE))
+    if is_train:
+        min_size, max_size, style = inp.MIN_SIZE_TRAIN, inp.MAX_SIZE_TRAIN, inp.get("MIN_SIZE_TRAIN_SAMPLING", "choice")
+    else:
+        min_size, max_size, style = inp.MIN_SIZE_TEST, inp.MAX_SIZE_TEST, "choice"
+    augs.append(ResizeShortestEdge(min_size if isinstance(min_size, int) else tuple(min_size), max_size, style))
+    if is_train and flip != "none":
+        augs.append(RandomFlip(horizontal=flip == "horizontal", vertical=flip == "vertical"))
+    return augs
+
+
+class ViewParams:
+    """what one image's pass through the full chain drew: the window [y0, y0 + h) x [x0, x0 + w) of the raw_h x raw_w image is
+    resized to (new_h, new_w), flipped left-right (hflip) and / or upside down (vflip); swap_rb exchanges channels 0 and 2"""
+    __slots__ = ("raw_h", "raw_w", "y0", "x0", "h", "w", "new_h", "new_w", "hflip", "vflip", "swap_rb")
+
+    def __init__(self, raw_h: int, raw_w: int, y0: int, x0: int, h: int, w: int, new_h: int, new_w: int, hflip: bool = False,
+                 vflip: bool = False, swap_rb: bool = False):
+        self.raw_h, self.raw_w, self.y0, self.x0, self.h, self.w = int(raw_h), int(raw_w), int(y0), int(x0), int(h), int(w)
+        self.new_h, self.new_w, self.hflip, self.vflip, self.swap_rb = int(new_h), int(new_w), bool(hflip), bool(vflip), bool(swap_rb)
+
+    @classmethod
+    def whole(cls, p: WeakParams, swap_rb: bool = False) -> "ViewParams":
+        """the two-stage chain's parameters as a window that covers the image"""
+        return cls(p.h, p.w, 0, 0, p.h, p.w, p.new_h, p.new_w, hflip=p.flip, swap_rb=swap_rb)
+
+    def __eq__(self, other):
+        return isinstance(other, ViewParams) and all(getattr(self, s) == getattr(other, s) for s in self.__slots__)
+
+    def __repr__(self):
+        return (f"ViewParams({self.raw_h}, {self.raw_w}, {self.y0}, {self.x0}, {self.h}, {self.w}, {self.new_h}, {self.new_w}, "
+                f"hflip={self.hflip}, vflip={self.vflip}, swap_rb={self.swap_rb})")
+
+
+def draw_view_params(augs, h: int, w: int, np_rng=np.random, swap_rb: bool = False) -> ViewParams:
+    """consume `np_rng` as detectron2's AugmentationList does for one h x w image and the chain of `get_view_augs`: the crop
+    draws, the size draw for the CROPPED size, the flip draw.  `swap_rb` is not drawn: it is the image's channel order against
+    INPUT.FORMAT.  A crop after the resize or the flip is not the mapper's chain and is refused."""
+    if isinstance(np_rng, np.random.Generator):
+        raise TypeError("draw_view_params: pass np.random or a RandomState, not a numpy Generator")
+    y0 = x0 = 0
+    ch, cw = int(h), int(w)
+    new_h, new_w, hflip, vflip, resized = ch, cw, False, False, False
+    for a in augs:
+        if isinstance(a, RandomCrop):
+            if resized or hflip or vflip or (ch, cw) != (int(h), int(w)):
+                raise ValueError("draw_view_params: RandomCrop must be the first stage, once")
+            y0, x0, ch, cw = a.get_params(ch, cw, np_rng)
+            new_h, new_w = ch, cw
+        elif isinstance(a, ResizeShortestEdge):
+            new_h, new_w = a.get_params(new_h, new_w, np_rng)
+            resized = True
+        elif isinstance(a, RandomFlip):
+            if a.get_params(np_rng):
+                hflip, vflip = hflip ^ a.horizontal, vflip ^ a.vertical
+        else:
+            raise ValueError(f"draw_view_params: {type(a).__name__} is not a stage of get_view_augs")
+    return ViewParams(h, w, y0, x0, ch, cw, new_h, new_w, hflip, vflip, swap_rb)
+
+
+def transform_view_boxes(boxes: np.ndarray, p: ViewParams) -> np.ndarray:
+    """`transform_boxes` under (CropTransform, ResizeTransform, HFlipTransform | VFlipTransform), float64 (parity unpinned):
+    corners minus (x0, y0), scaled by new_w / w and new_h / h of the window, x -> new_w - x and / or y -> new_h - y, their
+    min / max, clip(min=0), then the minimum with [W, H, W, H]."""
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+    idxs = np.array([(0, 1), (2, 1), (0, 3), (2, 3)]).flatten()
+    coords = b[:, idxs].reshape(-1, 2).copy()
+    coords[:, 0] -= p.x0
+    coords[:, 1] -= p.y0
+    coords[:, 0] = coords[:, 0] * (p.new_w * 1.0 / p.w)
+    coords[:, 1] = coords[:, 1] * (p.new_h * 1.0 / p.h)
+    if p.hflip:
+        coords[:, 0] = p.new_w - coords[:, 0]
+    if p.vflip:
+        coords[:, 1] = p.new_h - coords[:, 1]
+    coords = coords.reshape(-1, 4, 2)
+    out = np.concatenate((coords.min(axis=1), coords.max(axis=1)), axis=1).clip(min=0)
+    return np.minimum(out, [p.new_w, p.new_h, p.new_w, p.new_h])
