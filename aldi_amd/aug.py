@@ -479,7 +479,7 @@ def strong_views(weak_views: Sequence[torch.Tensor], augs, chw: bool = True, np_
 # below is Pillow's precompute_coeffs / normalize_coeffs_8bpc in its operation order and is pinned to Pillow's bytes by
 # tests/golden/pil_bilinear.npz.  The detectron2 pieces (output shape, draw order, box transform) restate the published v0.6
 # behaviour: PARITY UNPINNED, as oracle/aug_ops.py labels its detectron2 half.
-_GEOM_CHW_IN, _GEOM_CHW_OUT, _GEOM_HFLIP, _GEOM_FUSED = 1, 2, 4, 8
+_GEOM_CHW_IN, _GEOM_CHW_OUT, _GEOM_HFLIP, _GEOM_FUSED, _GEOM_VFLIP, _GEOM_SWAP_RB = 1, 2, 4, 8, 16, 32
 _GEOM_TH, _GEOM_TW = 16, 64
 _PRECISION_BITS = 32 - 8 - 2
 
@@ -490,7 +490,9 @@ class _GeomDesc(ctypes.Structure):
                 ("h", ctypes.c_int), ("w", ctypes.c_int), ("new_h", ctypes.c_int), ("new_w", ctypes.c_int), ("flags", ctypes.c_int),
                 ("xk_off", ctypes.c_int), ("xb_off", ctypes.c_int), ("xks", ctypes.c_int),
                 ("yk_off", ctypes.c_int), ("yb_off", ctypes.c_int), ("yks", ctypes.c_int),
-                ("tile_begin", ctypes.c_int), ("h_begin", ctypes.c_int), ("v_begin", ctypes.c_int)]
+                ("tile_begin", ctypes.c_int), ("h_begin", ctypes.c_int), ("v_begin", ctypes.c_int),
+                # the appended tail: the raw image's size and the window's origin; all zero = the window is the whole image
+                ("src_h", ctypes.c_int), ("src_w", ctypes.c_int), ("y0", ctypes.c_int), ("x0", ctypes.c_int)]
 
 
 class ResizeShortestEdge:
@@ -642,27 +644,13 @@ def _image_layout(img: torch.Tensor, p: WeakParams, chw_in: Optional[bool]) -> b
     raise ValueError(f"weak_views: image of shape {tuple(img.shape)} for parameters drawn for {p.h}x{p.w}")
 
 
-def launch_weak_views(images: Sequence[torch.Tensor], params: Sequence[WeakParams], chw_out: bool = True,
-                      chw_in=None, outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
-    """the device half of `weak_views`: one pinned upload (descriptors + tables), then one to three launches on the current
-    stream -- the fused kernel, and the two-pass arm for the images aldi_geom_plan keeps off it.  `outs`: the caller's own
-    output tensors (contiguous, of the output shapes) instead of fresh ones.  `chw_in`: None = each image's layout is read off its
-    shape and its parameters' raw size; a bool, or one per image, settles it."""
+def _launch_geom(images, vparams, layouts, chw_out: bool, outs, who: str) -> List[torch.Tensor]:
+    """the one device half of the weak and the windowed views: `vparams` are ViewParams already checked against `images`; one pinned
+    upload (descriptors + tables of the WINDOWS' sizes), then one to three launches on the current stream"""
     n = len(images)
-    if n == 0:
-        return []
-    if len(params) != n:
-        raise ValueError("launch_weak_views: one WeakParams per image")
-    layouts = []
-    for v, p, c in zip(images, params, chw_in if isinstance(chw_in, (list, tuple)) else [chw_in] * n):
-        layouts.append(_image_layout(v, p, c))
-        if not (v.is_cuda and v.is_contiguous()):
-            raise ValueError("launch_weak_views expects contiguous CUDA images")
-        if min(p.h, p.w, p.new_h, p.new_w) < 1:
-            raise ValueError(f"launch_weak_views: empty image in {p}")
     # the tables of the batch, one copy per distinct axis; layout of the upload: [descriptors][tables]
     slots, tabs, nints = {}, [], 1                               # (int 0 is a dummy: `tables` is never an empty buffer)
-    for p in params:
+    for p in vparams:
         for insz, outsz in ((p.w, p.new_w), (p.h, p.new_h)):
             if insz != outsz and (insz, outsz) not in slots:
                 k, b = resize_tables(insz, outsz)
@@ -681,20 +669,23 @@ def launch_weak_views(images: Sequence[torch.Tensor], params: Sequence[WeakParam
     for o, k, b in tabs:
         tab[o: o + k.size] = k.reshape(-1)
         tab[o + k.size: o + k.size + b.size] = b.reshape(-1)
-    shapes = [(3, p.new_h, p.new_w) if chw_out else (p.new_h, p.new_w, 3) for p in params]
+    shapes = [(3, p.new_h, p.new_w) if chw_out else (p.new_h, p.new_w, 3) for p in vparams]
     if outs is None:
         outs = [torch.empty(sh, dtype=torch.uint8, device=v.device) for v, sh in zip(images, shapes)]
     else:
         outs = list(outs)
         if len(outs) != n or any(not (o.is_cuda and o.dtype == torch.uint8 and o.is_contiguous() and tuple(o.shape) == sh) for o, sh in zip(outs, shapes)):
-            raise ValueError(f"launch_weak_views: `outs` must be contiguous CUDA uint8 tensors of shapes {shapes}")
+            raise ValueError(f"{who}: `outs` must be contiguous CUDA uint8 tensors of shapes {shapes}")
     keep = []                                                    # the two-pass arm's scratch images (stream-ordered: freed after the launches)
     tiles = hblocks = vblocks = 0
     fused = ctypes.c_int(0)
-    for i, (v, p, chw) in enumerate(zip(images, params, layouts)):
+    for i, (v, p, chw) in enumerate(zip(images, vparams, layouts)):
         d = descs[i]
         d.src, d.dst, d.h, d.w, d.new_h, d.new_w = v.data_ptr(), outs[i].data_ptr(), p.h, p.w, p.new_h, p.new_w
-        d.flags = (_GEOM_CHW_IN if chw else 0) | (_GEOM_CHW_OUT if chw_out else 0) | (_GEOM_HFLIP if p.flip else 0)
+        d.flags = ((_GEOM_CHW_IN if chw else 0) | (_GEOM_CHW_OUT if chw_out else 0) | (_GEOM_HFLIP if p.hflip else 0)
+                   | (_GEOM_VFLIP if p.vflip else 0) | (_GEOM_SWAP_RB if p.swap_rb else 0))
+        if (p.y0, p.x0, p.h, p.w) != (0, 0, p.raw_h, p.raw_w):   # (the tail stays zero for a window that is the whole image)
+            d.src_h, d.src_w, d.y0, d.x0 = p.raw_h, p.raw_w, p.y0, p.x0
         if p.w != p.new_w:
             d.xk_off, d.xb_off, d.xks = slots[(p.w, p.new_w)]
         yb = None
@@ -716,6 +707,27 @@ def launch_weak_views(images: Sequence[torch.Tensor], params: Sequence[WeakParam
     _upload(dev, host)
     L.call("aldi_geom_batch_resize", dbase, n, dbase + off_tab, tiles, hblocks, vblocks, ops.stream_ptr())
     return outs
+
+
+def launch_weak_views(images: Sequence[torch.Tensor], params: Sequence[WeakParams], chw_out: bool = True,
+                      chw_in=None, outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """the device half of `weak_views`: one pinned upload (descriptors + tables), then one to three launches on the current
+    stream -- the fused kernel, and the two-pass arm for the images aldi_geom_plan keeps off it.  `outs`: the caller's own
+    output tensors (contiguous, of the output shapes) instead of fresh ones.  `chw_in`: None = each image's layout is read off its
+    shape and its parameters' raw size; a bool, or one per image, settles it."""
+    n = len(images)
+    if n == 0:
+        return []
+    if len(params) != n:
+        raise ValueError("launch_weak_views: one WeakParams per image")
+    layouts = []
+    for v, p, c in zip(images, params, chw_in if isinstance(chw_in, (list, tuple)) else [chw_in] * n):
+        layouts.append(_image_layout(v, p, c))
+        if not (v.is_cuda and v.is_contiguous()):
+            raise ValueError("launch_weak_views expects contiguous CUDA images")
+        if min(p.h, p.w, p.new_h, p.new_w) < 1:
+            raise ValueError(f"launch_weak_views: empty image in {p}")
+    return _launch_geom(images, [ViewParams.whole(p) for p in params], layouts, chw_out, outs, "launch_weak_views")
 
 
 def weak_views(images: Sequence[torch.Tensor], params: Sequence[WeakParams], chw_out: bool = True, stream=None,
@@ -764,7 +776,8 @@ def transform_instances(inst: dict, p) -> dict:
 # ------------------------------------------------------------------------------------------------ the full chain, host half
 # detectron2's whole train-time mapper chain for a decoded image -- [RandomCrop] + ResizeShortestEdge + [RandomFlip horizontal |
 # vertical] -- as DRAWS and box arithmetic only: what a view with a source window has to be told, and what it does to the boxes.
-# Nothing here touches the device; `launch_weak_views` runs the two-stage chain only.  The two-stage entries above stay as they are.
+# Nothing in this block touches the device: `launch_views` at the end of the file is the device half, and
+# `launch_weak_views` is the same launch for a window that covers the image.  The two-stage entries above stay as they are.
 # The detectron2 pieces restate the published v0.6 behaviour: PARITY UNPINNED.
 class RandomCrop:
     """detectron2 RandomCrop (parity unpinned).  `get_params` draws from `np_rng` what `get_transform` draws from np.random, in
@@ -895,3 +908,48 @@ def transform_view_boxes(boxes: np.ndarray, p: ViewParams) -> np.ndarray:
     coords = coords.reshape(-1, 4, 2)
     out = np.concatenate((coords.min(axis=1), coords.max(axis=1)), axis=1).clip(min=0)
     return np.minimum(out, [p.new_w, p.new_h, p.new_w, p.new_h])
+
+
+# ------------------------------------------------------------------------------------------------ the full chain, device half
+def _check_window(p: ViewParams, who: str):
+    """the window must be a non-empty part of the raw image, the output non-empty: what the kernels would otherwise refuse silently"""
+    if min(p.h, p.w, p.new_h, p.new_w, p.raw_h, p.raw_w) < 1:
+        raise ValueError(f"{who}: empty window or image in {p}")
+    if p.y0 < 0 or p.x0 < 0 or p.y0 + p.h > p.raw_h or p.x0 + p.w > p.raw_w:
+        raise ValueError(f"{who}: the window is not inside the {p.raw_h}x{p.raw_w} image in {p}")
+
+
+def launch_views(images: Sequence[torch.Tensor], params: Sequence[ViewParams], chw_out: bool = True, chw_in=None,
+                 outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """the device half of `views`: as `launch_weak_views`, for the full chain.  `images` are the RAW images (raw_h x raw_w, their layout
+    read off the shape against the raw size, `chw_in` as there); tables and the choice of the arm follow the WINDOW's sizes; the
+    kernels read only the window, flip and exchange R and B at the store.  Everything is checked before the first device call."""
+    n = len(images)
+    if n == 0:
+        return []
+    if len(params) != n:
+        raise ValueError("launch_views: one ViewParams per image")
+    layouts = []
+    for v, p, c in zip(images, params, chw_in if isinstance(chw_in, (list, tuple)) else [chw_in] * n):
+        if not isinstance(p, ViewParams):
+            raise ValueError(f"launch_views: expected a ViewParams, got {type(p).__name__} (ViewParams.whole(p) turns a WeakParams into one)")
+        _check_window(p, "launch_views")
+        try:
+            layouts.append(_image_layout(v, WeakParams(p.raw_h, p.raw_w, p.new_h, p.new_w), c))
+        except ValueError as e:
+            raise ValueError(str(e).replace("weak_views", "launch_views") + f" (raw size {p.raw_h}x{p.raw_w})") from None
+        if not (v.is_cuda and v.is_contiguous()):
+            raise ValueError("launch_views expects contiguous CUDA images")
+    return _launch_geom(images, list(params), layouts, chw_out, outs, "launch_views")
+
+
+def views(images: Sequence[torch.Tensor], params: Sequence[ViewParams], chw_out: bool = True, stream=None, chw_in=None,
+          outs: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """Batched views of the full mapper chain: image i's window params[i].(y0, x0, h, w) is resized to (new_h, new_w) as Pillow's
+    BILINEAR resize of `raw[y0:y0+h, x0:x0+w]` does, byte for byte, then flipped left-right (hflip) and / or upside down (vflip), and
+    channels 0 and 2 change places when swap_rb.  Outputs are (3, new_h, new_w) when `chw_out` else (new_h, new_w, 3), on `stream`
+    (default: the current stream)."""
+    if stream is None:
+        return launch_views(images, params, chw_out, chw_in, outs)
+    with torch.cuda.stream(stream):
+        return launch_views(images, params, chw_out, chw_in, outs)

@@ -167,6 +167,11 @@ def add_aldi_config(cfg: CfgNode):
     _C.DATASETS.UNLABELED = tuple()
     _C.DATASETS.BATCH_CONTENTS = ("labeled_weak",)
     _C.DATASETS.BATCH_RATIOS = (1,)
+    # the loaders read the datasets named in DATASETS.TRAIN / UNLABELED / TEST from disk (every name must be in the DatasetCatalog:
+    # aldi_amd/datasets.py; nothing is registered implicitly), decode on DATALOADER.NUM_WORKERS threads (at most 16; no worker processes)
+    # and build every view on the device from the full mapper chain -- INPUT.CROP.*, ResizeShortestEdge, INPUT.RANDOM_FLIP horizontal or
+    # vertical, INPUT.FORMAT -- so AUG.DEVICE_WEAK must be on.  Off: the synthetic loaders, whatever the names say
+    _C.DATASETS.FILES = False
 
     _C.AUG = CN()
     _C.AUG.WEAK_INCLUDES_MULTISCALE = True

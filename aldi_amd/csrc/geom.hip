@@ -12,7 +12,16 @@
 //     downscales, whose row window (~ 16 * scale + 2 * ceil(scale) + 1 rows) does not fit, and is the plain reference arm.
 // Every source index is clamped into [0, insz) by axis_taps whatever the tables say; an LDS row outside the staged window is
 // skipped.
+//
+// The full mapper chain: detectron2's RandomCrop slices the decoded array BEFORE the resize, so a cropped view is
+// the same resize of a window of the raw image.  The descriptor's tail (src_h, src_w, y0, x0) says where the h x w window lies; all three
+// kernels read the source through it (window_of), the tables are those of the window's sizes, and axis_taps clamps every tap into the
+// window, so nothing outside the window is read, let alone outside the image; a window that is not inside the raw image makes every
+// kernel return for that image.  The vertical flip and the R <-> B exchange are per-pixel permutations that commute with the resize:
+// they sit at the store, next to the horizontal flip.
 #include "common.h"
+
+static_assert(sizeof(aldi_geom_desc) == 3 * sizeof(void*) + 18 * sizeof(int), "aldi_geom_desc: aldi_amd/aug.py _GeomDesc mirrors this layout");
 
 namespace {
 
@@ -66,11 +75,26 @@ __device__ __forceinline__ uint8_t fix_u8(int acc) {
     return (uint8_t)(acc < 0 ? 0 : (acc > 255 ? 255 : acc));
 }
 
-// pixel (r, mn + t), t < cnt, of a source image weighted along its row
-__device__ __forceinline__ void hpass_px(const uint8_t* __restrict__ src, bool chw, long plane, int w, int r, int mn, int cnt, const int* k,
+// the source window of one image inside its raw image (the descriptor's tail; all zero = the window is the whole image): pixel
+// (r, c) of the window is raw pixel base + r * stride + c, a CHW plane is `plane` pixels.  ok = false: the window is not inside the
+// raw image and nothing of it may be read.
+struct Window {
+    long base, plane;
+    int stride;
+    bool ok;
+};
+
+__host__ __device__ __forceinline__ Window window_of(const aldi_geom_desc& d) {
+    if (!(d.src_h | d.src_w | d.y0 | d.x0)) return Window{0, (long)d.h * d.w, d.w, d.h > 0 && d.w > 0};
+    const bool ok = d.h > 0 && d.w > 0 && d.x0 >= 0 && d.y0 >= 0 && (long)d.x0 + d.w <= d.src_w && (long)d.y0 + d.h <= d.src_h;
+    return Window{(long)d.y0 * d.src_w + d.x0, (long)d.src_h * d.src_w, d.src_w, ok};
+}
+
+// pixel (r, mn + t), t < cnt, of a source window weighted along its row
+__device__ __forceinline__ void hpass_px(const uint8_t* __restrict__ src, bool chw, const Window& win, int r, int mn, int cnt, const int* k,
                                          uint8_t out[3]) {
     int a0 = kHalf, a1 = kHalf, a2 = kHalf;
-    const long o = (long)r * w + mn;
+    const long o = win.base + (long)r * win.stride + mn, plane = win.plane;
     if (chw) {
         for (int t = 0; t < cnt; ++t) {
             const int c = coef(k, t);
@@ -91,10 +115,12 @@ __device__ __forceinline__ void hpass_px(const uint8_t* __restrict__ src, bool c
 }
 
 __device__ __forceinline__ void store_px(const aldi_geom_desc& d, int y, int x, const uint8_t v[3]) {
-    const int xo = (d.flags & ALDI_GEOM_HFLIP) ? d.new_w - 1 - x : x;
-    const long px = (long)y * d.new_w + xo, plane = (long)d.new_h * d.new_w;
-    if (d.flags & ALDI_GEOM_CHW_OUT) { d.dst[px] = v[0]; d.dst[px + plane] = v[1]; d.dst[px + 2 * plane] = v[2]; }
-    else { d.dst[px * 3] = v[0]; d.dst[px * 3 + 1] = v[1]; d.dst[px * 3 + 2] = v[2]; }
+    const int xo = (d.flags & ALDI_GEOM_HFLIP) ? d.new_w - 1 - x : x, yo = (d.flags & ALDI_GEOM_VFLIP) ? d.new_h - 1 - y : y;
+    const long px = (long)yo * d.new_w + xo, plane = (long)d.new_h * d.new_w;
+    const bool swap = d.flags & ALDI_GEOM_SWAP_RB;
+    const uint8_t c0 = swap ? v[2] : v[0], c2 = swap ? v[0] : v[2];
+    if (d.flags & ALDI_GEOM_CHW_OUT) { d.dst[px] = c0; d.dst[px + plane] = v[1]; d.dst[px + 2 * plane] = c2; }
+    else { d.dst[px * 3] = c0; d.dst[px * 3 + 1] = v[1]; d.dst[px * 3 + 2] = c2; }
 }
 
 __global__ __launch_bounds__(256) void resize_fused_kernel(const aldi_geom_desc* __restrict__ desc, int n, const int* __restrict__ tab) {
@@ -104,7 +130,8 @@ __global__ __launch_bounds__(256) void resize_fused_kernel(const aldi_geom_desc*
     if (!(d.flags & ALDI_GEOM_FUSED)) return;
     const int tiles_x = (d.new_w + kTW - 1) / kTW, t = (int)blockIdx.x - d.tile_begin;
     const int y0 = (t / tiles_x) * kTH, x0 = (t % tiles_x) * kTW;
-    if (y0 >= d.new_h) return;
+    const Window win = window_of(d);
+    if (!win.ok || y0 >= d.new_h) return;
     const int th = d.new_h - y0 < kTH ? d.new_h - y0 : kTH, tw = d.new_w - x0 < kTW ? d.new_w - x0 : kTW;
     const Axis X = axis_of(tab, d.xk_off, d.xb_off, d.xks, d.w), Y = axis_of(tab, d.yk_off, d.yb_off, d.yks, d.h);
     int r0, c0, r1, c1;
@@ -114,13 +141,12 @@ __global__ __launch_bounds__(256) void resize_fused_kernel(const aldi_geom_desc*
     const int nrows = r1 + c1 - r0;                      // bounds are non-decreasing: [r0, r1 + c1) covers every row of the tile
     if (nrows <= 0 || nrows > kRows) return;             // (aldi_geom_plan sends such an image through the two-pass arm)
     const bool chw = d.flags & ALDI_GEOM_CHW_IN;
-    const long plane = (long)d.h * d.w;
     for (int q = threadIdx.x; q < nrows * tw; q += 256) {
         const int lr = q / tw, lc = q - lr * tw;
         int mn, cnt;
         axis_taps(X, x0 + lc, mn, cnt, kk);
         uint8_t v[3];
-        hpass_px(d.src, chw, plane, d.w, r0 + lr, mn, cnt, kk, v);
+        hpass_px(d.src, chw, win, r0 + lr, mn, cnt, kk, v);
         uint8_t* s = s_rows + (lr * kTW + lc) * 3;
         s[0] = v[0]; s[1] = v[1]; s[2] = v[2];
     }
@@ -149,14 +175,15 @@ __global__ __launch_bounds__(256) void resize_h_kernel(const aldi_geom_desc* __r
     const aldi_geom_desc& d = desc[i];
     if ((d.flags & ALDI_GEOM_FUSED) || !d.tmp) return;
     const long p = ((long)blockIdx.x - d.h_begin) * 256 + threadIdx.x;
-    if (p >= (long)d.h * d.new_w) return;
+    const Window win = window_of(d);
+    if (!win.ok || p >= (long)d.h * d.new_w) return;
     const int r = (int)(p / d.new_w), x = (int)(p - (long)r * d.new_w);
     const Axis X = axis_of(tab, d.xk_off, d.xb_off, d.xks, d.w);
     int mn, cnt;
     const int* kk;
     axis_taps(X, x, mn, cnt, kk);
     uint8_t v[3];
-    hpass_px(d.src, d.flags & ALDI_GEOM_CHW_IN, (long)d.h * d.w, d.w, r, mn, cnt, kk, v);
+    hpass_px(d.src, d.flags & ALDI_GEOM_CHW_IN, win, r, mn, cnt, kk, v);
     uint8_t* o = d.tmp + p * 3;
     o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
 }
@@ -167,8 +194,8 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const aldi_geom_desc* __r
     const aldi_geom_desc& d = desc[i];
     if ((d.flags & ALDI_GEOM_FUSED) || !d.tmp) return;
     const long p = ((long)blockIdx.x - d.v_begin) * 256 + threadIdx.x;
-    if (p >= (long)d.new_h * d.new_w) return;
-    const int y = (int)(p / d.new_w), x = (int)(p - (long)y * d.new_w);
+    if (!window_of(d).ok || p >= (long)d.new_h * d.new_w) return;   // (the scratch image of such a window was never written)
+    const int y =(int)(p / d.new_w), x = (int)(p - (long)y * d.new_w);
     const Axis Y = axis_of(tab, d.yk_off, d.yb_off, d.yks, d.h);
     int mn, cnt;
     const int* kk;
@@ -196,6 +223,13 @@ extern "C" int aldi_geom_plan(const int* ybounds, int h, int new_h, int* fused) 
         }
     }
     *fused = 1;
+    return ALDI_OK;
+}
+
+extern "C" int aldi_geom_window(const aldi_geom_desc* desc, long* base, long* plane, int* stride, int* inside) {
+    if (!desc || !base || !plane || !stride || !inside) return aldi_set_error_msg(ALDI_ERR_ARG, "geom_window: bad args");
+    const Window win = window_of(*desc);
+    *base = win.base; *plane = win.plane; *stride = win.stride; *inside = win.ok ? 1 : 0;
     return ALDI_OK;
 }
 

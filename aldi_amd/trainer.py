@@ -854,6 +854,8 @@ class ALDITrainer(DefaultTrainer):
         batch_contents = contents
         world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         rank = dist.get_rank() if world > 1 else 0
+        if cfg.DATASETS.get("FILES", False):
+            return cls._build_file_train_loader(cfg, labeled_bs // world, unlabeled_bs // world, contents, rank, world)
         syn = cfg.get("SYNTHETIC", {})
         h, w = syn.get("HEIGHT", 800), syn.get("WIDTH", 1333)
         K = _num_classes(cfg)
@@ -880,6 +882,66 @@ class ALDITrainer(DefaultTrainer):
                 unlabeled_loader = stage(unlabeled_loader, False, "unlabeled_strong")
         return WeakStrongDataloader(labeled_loader, unlabeled_loader, batch_contents)
 
+    # ---- DATASETS.FILES: the datasets on disk
+    @staticmethod
+    def _check_file_datasets(cfg, names):
+        """DATASETS.FILES needs the device view (the host resizes nothing) and registered names (nothing is registered implicitly)"""
+        from .datasets import DatasetCatalog
+        if not cfg.AUG.get("DEVICE_WEAK", False):
+            raise ValueError("DATASETS.FILES needs AUG.DEVICE_WEAK: the decoded images are cropped, resized and flipped on the device only")
+        missing = [n for n in names if n not in DatasetCatalog]
+        if missing:
+            raise KeyError(f"DATASETS.FILES: not in the DatasetCatalog: {missing} (registered: {DatasetCatalog.list()}); register them "
+                           "with aldi_amd.datasets.register_coco_instances / register_reference_datasets")
+
+    @classmethod
+    def _build_file_train_loader(cls, cfg, labeled_bs, unlabeled_bs, contents, rank, world):
+        """the labeled loader reads DATASETS.TRAIN (DATALOADER.FILTER_EMPTY_ANNOTATIONS as in detectron2), the unlabeled one
+        DATASETS.UNLABELED (nothing filtered, instances emptied); each is FileDetectionLoader -> the one device stage with the full
+        chain `get_view_augs(cfg, True)`, so INPUT.CROP.* and INPUT.RANDOM_FLIP "vertical" work here"""
+        from .aug import get_strong_augs, get_view_augs
+        from .dataloader import FileDetectionLoader, TrainingSampler, file_sampler_seed
+        from .datasets import get_detection_dataset_dicts
+        from .mapper import DatasetMapper
+        train, unl = list(cfg.DATASETS.TRAIN), list(cfg.DATASETS.UNLABELED)
+        cls._check_file_datasets(cfg, (train if labeled_bs > 0 else []) + (unl if unlabeled_bs > 0 else []))
+        for bs, names, key in ((labeled_bs, train, "TRAIN"), (unlabeled_bs, unl, "UNLABELED")):
+            if bs > 0 and not names:
+                raise ValueError(f"DATASETS.FILES: the batch asks for {key.lower()} images but DATASETS.{key} is empty")
+        base = max(int(cfg.SEED), 0)
+        device_strong = bool(cfg.AUG.get("DEVICE_STRONG", False))
+        view = get_view_augs(cfg, True)
+        threads = int(cfg.DATALOADER.NUM_WORKERS)
+
+        def domain(bs, names, labeled, part):
+            if bs <= 0:
+                return None
+            dicts = get_detection_dataset_dicts(names, filter_empty=bool(cfg.DATALOADER.FILTER_EMPTY_ANNOTATIONS) if labeled else False)
+            if not dicts:
+                raise ValueError(f"DATASETS.FILES: {names} have no images left after DATALOADER.FILTER_EMPTY_ANNOTATIONS")
+            mapper = DatasetMapper(cfg, True, labeled)
+            files = FileDetectionLoader(dicts, mapper, bs, TrainingSampler(len(dicts), True, file_sampler_seed(base, labeled), rank, world), threads)
+            return DeviceStrongAugLoader(files, get_strong_augs(cfg, labeled) if device_strong and part in contents else None,
+                                         device_strong_seed(base, rank, labeled), weak=view, weak_seed=device_weak_seed(base, rank, labeled),
+                                         view=True, swap_rb=mapper.swap_rb)
+        return WeakStrongDataloader(domain(labeled_bs, train, True, "labeled_strong"), domain(unlabeled_bs, unl, False, "unlabeled_strong"),
+                                    contents)
+
+    @classmethod
+    def _build_file_test_loader(cls, cfg, dataset_name):
+        """a lazy, finite loader over the registered dataset (one image per batch, this rank's InferenceSampler shard) + its records"""
+        from .aug import get_view_augs
+        from .dataloader import DeviceTestViewLoader, FileDetectionLoader, InferenceSampler
+        from .datasets import DatasetCatalog
+        from .mapper import DatasetMapper
+        cls._check_file_datasets(cfg, [dataset_name])
+        records = DatasetCatalog.get(dataset_name)
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        rank = dist.get_rank() if world > 1 else 0
+        mapper = DatasetMapper(cfg, False, True)
+        files = FileDetectionLoader(records, mapper, 1, InferenceSampler(len(records), rank, world), int(cfg.DATALOADER.NUM_WORKERS))
+        return DeviceTestViewLoader(files, get_view_augs(cfg, False), mapper.swap_rb, cfg.MODEL.DEVICE), records
+
     def before_step(self):
         super(ALDITrainer, self).before_step()
         if self.cfg.EMA.ENABLED:
@@ -894,7 +956,10 @@ class ALDITrainer(DefaultTrainer):
     # ---- evaluation (reference aldi/trainer.py:166-196: COCO evaluator, EvalHook on the EMA model, BestCheckpointer on bbox/AP50)
     @classmethod
     def build_test_loader(cls, cfg, dataset_name):
-        """synthetic validation split: a finite list of batches of {image, image_id, height, width} + detectron2-format records"""
+        """synthetic validation split: a finite list of batches of {image, image_id, height, width} + detectron2-format records
+        (DATASETS.FILES: a lazy loader over the registered dataset `dataset_name` and its records)"""
+        if cfg.DATASETS.get("FILES", False):
+            return cls._build_file_test_loader(cfg, dataset_name)
         syn_ = cfg.get("SYNTHETIC", {})
         h, w = syn_.get("HEIGHT", 800), syn_.get("WIDTH", 1333)
         n, K = int(syn_.get("VAL_IMAGES", 8)), _num_classes(cfg)
@@ -942,7 +1007,7 @@ class ALDITrainer(DefaultTrainer):
             ev = evaluators[i] if evaluators is not None else cls.build_evaluator(cfg, name, dataset_dicts=records)
             # detectron2's InferenceSampler: every rank runs a disjoint shard of the test set, the evaluator gathers the
             # predictions on rank 0 (each detection counted once; the ground truth stays the full set)
-            results[name] = inference_on_dataset(model, loader[rank::world] if world > 1 else loader, ev)
+            results[name] = inference_on_dataset(model, loader[rank::world] if world > 1 and isinstance(loader, list) else loader, ev)   # (a file loader shards itself)
         return results[names[0]] if len(results) == 1 else results
 
     @classmethod

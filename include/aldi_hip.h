@@ -637,23 +637,34 @@ int aldi_np_mt_advance(unsigned int* key, int* pos, long n, long seg, unsigned i
  * int b[outsz][2] = (first input index, tap count); out = clip(((1 << 21) + sum_t in[first + t] * k[t]) >> 22, 0, 255).
  * Bit-identical to Pillow.
  * --------------------------------------------------------------------------------------- */
-enum { ALDI_GEOM_CHW_IN = 1, ALDI_GEOM_CHW_OUT = 2, ALDI_GEOM_HFLIP = 4, ALDI_GEOM_FUSED = 8 };
+enum { ALDI_GEOM_CHW_IN = 1, ALDI_GEOM_CHW_OUT = 2, ALDI_GEOM_HFLIP = 4, ALDI_GEOM_FUSED = 8, ALDI_GEOM_VFLIP = 16, ALDI_GEOM_SWAP_RB = 32 };
 enum { ALDI_GEOM_TH = 16, ALDI_GEOM_TW = 64,      /* output tile of the fused kernel */
        ALDI_GEOM_LDS_ROWS = 96 };                 /* input rows one tile may stage in LDS (x 64 pixels x 3 bytes = 18 KiB) */
 typedef struct aldi_geom_desc {
-    const unsigned char* src;                     /* device, uint8 HWC or CHW (flag CHW_IN), contiguous, h x w */
+    const unsigned char* src;                     /* device, uint8 HWC or CHW (flag CHW_IN), contiguous, src_h x src_w (h x w when the tail is zero) */
     unsigned char* dst;                           /* device, HWC or CHW (flag CHW_OUT), new_h x new_w */
     unsigned char* tmp;                           /* two-pass arm: h x new_w x 3 bytes of scratch; NULL with flag FUSED */
-    int h, w, new_h, new_w;
-    int flags;                                    /* CHW_IN, CHW_OUT, HFLIP (x -> new_w - 1 - x at the store), FUSED (the arm, from aldi_geom_plan) */
+    int h, w, new_h, new_w;                       /* h x w: the source WINDOW that is resized (the whole image when the tail is zero) */
+    int flags;                                    /* CHW_IN, CHW_OUT, HFLIP (x -> new_w - 1 - x at the store), FUSED (the arm, from aldi_geom_plan),
+                                                   * VFLIP (y -> new_h - 1 - y at the store), SWAP_RB (channels 0 and 2 exchanged at the store) */
     int xk_off, xb_off, xks;                      /* x tables: offsets in ints into `tables`, ksize; xks 0 = width kept, no horizontal pass */
     int yk_off, yb_off, yks;                      /* y tables, likewise */
     int tile_begin;                               /* first tile in the fused launch's grid (16 x 64 output tiles; no tiles unless FUSED) */
     int h_begin, v_begin;                         /* first block in the two-pass launches' grids (256 pixels per block; none with FUSED) */
+    /* the tail, appended: the raw image's rows and row length in pixels and the window's origin in it (detectron2's RandomCrop slices
+     * the decoded array before the resize: pixel (r, c) of the window is at (y0 + r) * src_w + x0 + c, the CHW plane stride is
+     * src_h * src_w).  All four zero = the window is the whole image (src_h = h, src_w = w, origin 0): a descriptor filled as before
+     * the tail existed behaves as before.  A window that is not inside the raw image (x0 < 0, y0 < 0, x0 + w > src_w, y0 + h > src_h)
+     * makes the kernels return for that image without reading. */
+    int src_h, src_w, y0, x0;
 } aldi_geom_desc;
 /* Host only: *fused = 1 when tuning knob resize_fused is on and every 16-row output tile's input row window, read from the
  * y bounds [new_h][2] (ignored when h == new_h), fits ALDI_GEOM_LDS_ROWS. */
 int aldi_geom_plan(const int* ybounds, int h, int new_h, int* fused);
+/* Host only: how the kernels read one (host) descriptor's source window -- the very function they call: window pixel (r, c) is raw
+ * pixel *base + r * *stride + c, a CHW plane is *plane pixels; *inside = 0 when the window is not inside the raw image (the kernels
+ * then return for that image without reading). */
+int aldi_geom_window(const aldi_geom_desc* desc, long* base, long* plane, int* stride, int* inside);
 /* N images in at most three launches: the fused kernel over ntiles tiles, then the two-pass arm's horizontal (nh_blocks) and
  * vertical (nv_blocks) launches for the images without flag FUSED.  desc and tables are device pointers. */
 int aldi_geom_batch_resize(const aldi_geom_desc* desc, int n, const int* tables, int ntiles, int nh_blocks, int nv_blocks, aldi_stream_t stream);
